@@ -62,7 +62,7 @@ const char* tsg_last_error(void);
 
 /* Measurement hook (bench.py's roofline line; never used by the product path).  tsg_time_next_launch(slot) arms the calling
  * thread: the NEXT launch of tsg_scdm_attn_fwd / tsg_scdm_gate_fwd (dtype TSG_F32S or TSG_BF16) or tsg_scdm_attn_bwd / tsg_scdm_gate_bwd
- * (their fused kernel) made by this thread is issued with hipExtLaunchKernel and the library-owned event pair of `slot`
+ * (their fused kernel) or tsg_moment_augment made by this thread is issued with hipExtLaunchKernel and the library-owned event pair of `slot`
  * (0 <= slot < 1024), which brackets that kernel alone -- the duration rocprofv3's kernel trace reports, without the dispatch gap an
  * event pair recorded around the call adds.  tsg_timed_launch_us(slot, &us) waits for the launch and returns its duration in
  * microseconds; TSG_E_SHAPE for a slot out of range or never used.  tsg_time_next_launch(-1) disarms.  Not valid while a stream capture is open.                        */
@@ -527,6 +527,27 @@ int tsg_sequence_masks(const int32_t* nfeats, const int32_t* spans, int32_t* vid
  *   video, out [B,T,D] (out != video); new_spans [B,2] = [cropin, cropin+len-1].                                            */
 int tsg_moment_translate(const void* video, const int32_t* spans, const int32_t* nfeats, const int32_t* cropin,
                          uint64_t seed, void* out, int32_t* new_spans, int B, int T, int D, int dtype, void* stream);
+/* tsg_moment_augment: the crop family of DataAugmentForTSG.aug_data (dataset/data_augment.py:28-156) for a whole batch in one
+ *   launch (csrc/augment.hip).  mode (TSG_AUG_*) picks the reference's candidate functions; per sample the apply gate
+ *   (np.random.rand() > aug_percentage skips; <= 0 never applies, >= 1 always), the candidate and the function's own
+ *   random.randint draws, over the reference's inclusive ranges and in its order, come from a counter-based hash of
+ *   (seed, b, draw slot).  The result is a plan int32 [B,4] = (op, a, b, c):
+ *     op 0 identity;  op 1 translate (a = cropin, as tsg_moment_translate);  op 2 crop (a = width, b = start: rows
+ *     [b, b+a) deleted, the rest shifts left, zero tail; span [s, e-a], nfeats - a);  op 3 cropout (a = width, b = out_start,
+ *     c = in_start: rows [b, b+a) overwritten with rows [c, c+a) of the input).  prot_gt_crop and both fallbacks of cropout
+ *     resolve to op 2.  plan non-NULL: used as given (the draws are skipped; fields are clamped to [0, T] and an op outside
+ *     0-3 acts as op 0 -- the library does not read device memory on the host, so the caller validates the ops); plan_out
+ *     (may be NULL) receives the plan used.  video, out [B,T,D] (out != video); dtype TSG_F32 (D % 4 == 0) or TSG_BF16 (bf16
+ *     storage, D % 8 == 0): rows are moved, never converted.  new_spans [B,2], new_nfeats [B] int32.                       */
+enum { TSG_AUG_TRANSLATE = 0,   /* gt_translate                                            */
+       TSG_AUG_CROP = 1,        /* gt_crop                                                 */
+       TSG_AUG_PROT_CROP = 2,   /* prot_gt_crop                                            */
+       TSG_AUG_CROPOUT = 3,     /* gt_cropout                                              */
+       TSG_AUG_ALL = 4,         /* 'all': prot_gt_crop or gt_cropout per sample            */
+       TSG_AUG_DEFAULT = 5 };   /* any other name (None): gt_crop or gt_cropout per sample */
+int tsg_moment_augment(const void* video, const int32_t* spans, const int32_t* nfeats, int mode, double aug_percentage,
+                       uint64_t seed, const int32_t* plan, int32_t* plan_out, void* out, int32_t* new_spans,
+                       int32_t* new_nfeats, int B, int T, int D, int dtype, void* stream);
 /* tsg_span_pred: span_pred (grounding/loss.py:53-70): (i, j) = argmax of triu(start_i + end_j) -- the zero-filled lower
  *   triangle takes part, the first maximum wins along j and then along i (torch.max).  start, end [B,T] fp32 ->
  *   pred [B,2] int64 = (i, j), score [B] fp32 = the maximum.  T <= 16384.                                                   */

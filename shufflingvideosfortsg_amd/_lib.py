@@ -90,6 +90,7 @@ _SIGNATURES = {
     "tsg_pool_clips": [_P] * 6 + [_I] * 4 + [_P],
     "tsg_sequence_masks": [_P] * 6 + [_I] * 2 + [_P],
     "tsg_moment_translate": [_P] * 4 + [c_uint64, _P, _P] + [_I] * 4 + [_P],
+    "tsg_moment_augment": [_P, _P, _P, _I, ctypes.c_double, c_uint64] + [_P] * 5 + [_I] * 4 + [_P],
     "tsg_span_pred": [_P] * 4 + [_I] * 3 + [_P],
     "tsg_mha_bwd": [_P] * 10 + [_I] * 6 + [c_float, _I, c_float, c_uint64, c_uint64, _I, _P],
 }

@@ -10,6 +10,8 @@ Two implementations of the same functions:
     (train.py:50-91 keys) from resident features."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -41,6 +43,118 @@ def gt_moment_translate(framestps, nfeats, video_feat, cropin_start=None, rng=No
     out = np.zeros(video_feat.shape) + 0.0
     out[0, :nfeats] = video_feat[0, order]
     return [cropin_start, cropin_start + n - 1], nfeats, out
+
+
+def _randint(rng):
+    if rng is None:
+        import random as rng           # the reference draws from the unseeded global ``random``
+    return rng.randint
+
+
+def _crop_rows(video_feat, crop_start, crop_width):
+    """np.delete of rows [crop_start, crop_start + crop_width) along axis 1, then zero-filled back to T rows
+    (data_augment.py:56-58).  Rows at or beyond T are not there to delete."""
+    T = video_feat.shape[1]
+    keep = [t for t in range(T) if not crop_start <= t < crop_start + crop_width]
+    out = np.zeros(video_feat.shape) + 0.0
+    out[0, :len(keep)] = video_feat[0, keep]
+    return out
+
+
+def gt_moment_crop(framestps, nfeats, video_feat, crop_width=None, crop_start=None, rng=None,
+                   min_crop_width_ratio=0.2, max_crop_width_ratio=0.5):
+    """``gt_crop`` (data_augment.py:38-63): delete ``crop_width`` clips starting at ``crop_start`` from inside the moment
+    [s, e]; the rest shifts left over a zero tail.  Width drawn in [ceil(.2 len), ceil(.5 len)] when not given or >= len,
+    start in [s, e - w + 1] when not given or outside [s, e] (``rng.randint``, inclusive).  Returns ([s, e - w], nfeats - w,
+    new feats); moments of length <= 1 are returned unchanged."""
+    s, e = framestps
+    n = e - s + 1
+    if n <= 1:
+        return list(framestps), nfeats, video_feat
+    randint = _randint(rng)
+    if crop_width is None or crop_width >= n:
+        crop_width = randint(int(np.ceil(n * min_crop_width_ratio)), int(np.ceil(n * max_crop_width_ratio)))
+    if crop_start is None or crop_start < s or crop_start > e:
+        crop_start = randint(s, e - crop_width + 1)
+    return [s, e - crop_width], nfeats - crop_width, _crop_rows(video_feat, crop_start, crop_width)
+
+
+def protected_gt_moment_crop(framestps, nfeats, video_feat, crop_width=None, crop_start=None, rng=None,
+                             min_crop_width_ratio=0.2, max_crop_width_ratio=0.5, protected_ratio=0.2):
+    """``prot_gt_crop`` (data_augment.py:65-93): ``gt_moment_crop`` inside the protected part [ps, pe] = [s + ceil(.2 len),
+    e - ceil(.2 len)] of the moment: width in [ceil(.2 (pe - ps)), ceil(.5 (pe - ps))], start in [ps, pe - w + 1].  pe - ps
+    is -1 or 0 for moments of 2-3 clips: width 0, a crop that deletes nothing."""
+    s, e = framestps
+    n = e - s + 1
+    if n <= 1:
+        return list(framestps), nfeats, video_feat
+    randint = _randint(rng)
+    ps, pe = s + int(np.ceil(n * protected_ratio)), e - int(np.ceil(n * protected_ratio))
+    if crop_width is None or crop_width > n:
+        crop_width = randint(int(np.ceil((pe - ps) * min_crop_width_ratio)), int(np.ceil((pe - ps) * max_crop_width_ratio)))
+    if crop_start is None or crop_start < s or crop_start > e:
+        crop_start = randint(ps, pe - crop_width + 1)
+    return [s, e - crop_width], nfeats - crop_width, _crop_rows(video_feat, crop_start, crop_width)
+
+
+def cropout_candidates(framestps, nfeats, crop_width, protected_ratio=0.2):
+    """The cropin starts ``gt_moment_cropout`` chooses from (data_augment.py:118-122): [0, psl - 1] if psl >= w and
+    [per, nfeats - w - 1] if nfeats - 1 - per >= w, where psl / per = s - ceil(.2 len) / e + ceil(.2 len)."""
+    s, e = framestps
+    c = int(np.ceil((e - s + 1) * protected_ratio))
+    psl, per = s - c, e + c
+    cand = list(range(psl)) if psl >= crop_width else []
+    if nfeats - 1 - per >= crop_width:
+        cand += list(range(per, nfeats - crop_width))
+    return cand
+
+
+def gt_moment_cropout(framestps, nfeats, video_feat, crop_width=None, cropout_start=None, cropin_start=None, rng=None,
+                      min_crop_width_ratio=0.2, max_crop_width_ratio=0.5, protected_ratio=0.2):
+    """``gt_cropout`` (data_augment.py:95-133): overwrite ``crop_width`` clips of the moment's protected part, starting at
+    ``cropout_start``, with the clips starting at ``cropin_start`` outside the moment (read from the original video); span and
+    nfeats stay.  Draws (``rng.randint``, inclusive) for what is not given: width in [ceil(.2 d), ceil(.5 d)] with
+    d = (e - ceil(.2 len)) - (s + ceil(.2 len)), cropout start in [s + ceil(.2 len), e - ceil(.2 len) - w + 1], cropin start
+    uniformly from ``cropout_candidates``.  Fallbacks as in the reference: w <= 0 -> ``gt_moment_crop`` with fresh draws; no
+    candidate -> ``gt_moment_crop(w, cropout_start)``."""
+    s, e = framestps
+    n = e - s + 1
+    if n <= 1:
+        return list(framestps), nfeats, video_feat
+    randint = _randint(rng)
+    c = int(np.ceil(n * protected_ratio))
+    psr, pel = s + c, e - c
+    if crop_width is None:
+        crop_width = randint(int(np.ceil((pel - psr) * min_crop_width_ratio)), int(np.ceil((pel - psr) * max_crop_width_ratio)))
+    if crop_width <= 0:
+        return gt_moment_crop(framestps, nfeats, video_feat, rng=rng, min_crop_width_ratio=min_crop_width_ratio,
+                              max_crop_width_ratio=max_crop_width_ratio)
+    if cropout_start is None:
+        cropout_start = randint(psr, pel - crop_width + 1)
+    cand = cropout_candidates(framestps, nfeats, crop_width, protected_ratio)
+    if not cand:
+        return gt_moment_crop(framestps, nfeats, video_feat, crop_width, cropout_start, rng=rng,
+                              min_crop_width_ratio=min_crop_width_ratio, max_crop_width_ratio=max_crop_width_ratio)
+    if cropin_start is None:
+        cropin_start = cand[randint(0, len(cand) - 1) if len(cand) > 1 else 0]
+    out = video_feat.copy()
+    out[0, cropout_start:cropout_start + crop_width] = video_feat[0, cropin_start:cropin_start + crop_width]
+    return list(framestps), nfeats, out
+
+
+def apply_plan(framestps, nfeats, video_feat, plan):
+    """One sample's resolved plan (op, a, b, c) -- see ``moment_augment_device`` -- applied with the numpy functions above."""
+    op, a, b, c = (int(x) for x in plan)
+    if op == 1:
+        return gt_moment_translate(framestps, nfeats, video_feat, a)
+    if op == 2:
+        s, e = framestps
+        return [s, e - a], nfeats - a, _crop_rows(video_feat, b, a)
+    if op == 3:
+        out = video_feat.copy()
+        out[0, b:b + a] = video_feat[0, c:c + a]
+        return list(framestps), nfeats, out
+    return list(framestps), nfeats, video_feat
 
 
 def synthetic_batch(B, T, N, video_dim=1024, word_dim=300, seed=1234, pair=False, device="cpu"):
@@ -220,3 +334,153 @@ def pair_batch_device(video, nfeats, spans, query, seed=0, cropin_start=None, ti
     out["gt"]["framestps"], out["pseudo_gt"]["framestps"] = sp.long(), psp.long()
     out["gt"]["timestps"] = timestps if timestps is not None else sp.float()
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the crop family of the augmentation on the device (csrc/augment.hip)
+# ---------------------------------------------------------------------------------------------------------------------
+
+# DataAugmentForTSG's mode names (data_augment.py:13-26) -> TSG_AUG_* of include/tsg_hip.h; None is the reference's fall-through
+# branch (argparse default of charades.py): gt_crop or gt_cropout per sample
+AUG_MODES = {"gt_translate": 0, "gt_crop": 1, "prot_gt_crop": 2, "gt_cropout": 3, "all": 4, None: 5}
+
+
+def aug_mode_code(mode):
+    """TSG_AUG_* code of a reference mode name.  'shuffle_temporal' raises NotImplementedError: the reference's aug_data passes
+    min_crop_width_ratio (0.2) as its seg_len (data_augment.py:36, :158-161), so that mode cannot run there either."""
+    if isinstance(mode, str) and mode == "shuffle_temporal":
+        raise NotImplementedError("aug_mode 'shuffle_temporal' is not supported: the reference's aug_data calls it with "
+                                  "seg_len = min_crop_width_ratio = 0.2 and it fails there too")
+    if mode not in AUG_MODES:
+        raise ValueError(f"unknown aug_mode {mode!r}; expected one of {sorted(k for k in AUG_MODES if k)} or None")
+    return AUG_MODES[mode]
+
+
+_M64 = (1 << 64) - 1
+
+
+def _splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+class _HashDraws:
+    """The device's draws for one sample (csrc/augment.hip: aug_hash / draw_int / draw_unit), slot by slot."""
+    GATE, FN, WIDTH, START, PICK, FB_WIDTH, FB_START = range(7)
+
+    def __init__(self, seed, b):
+        self.key = (int(seed) & _M64) ^ ((0xD1B54A32D192ED03 * (b + 1)) & _M64)
+
+    def _h(self, slot):
+        return _splitmix64(self.key ^ ((0xA0761D6478BD642F * (slot + 1)) & _M64))
+
+    def randint(self, slot, lo, hi):
+        return lo if hi <= lo else lo + (((self._h(slot) >> 32) * (hi - lo + 1)) >> 32)
+
+    def unit(self, slot):
+        return (self._h(slot) >> 11) * 2.0 ** -53
+
+
+def _ceil(x, r):
+    return math.ceil(x * r)
+
+
+def _draw_plan(d, code, p, s, e, nf):
+    """One sample's plan (op, a, b, c) as the device draws it (draw_plan in csrc/augment.hip)."""
+    n = e - s + 1
+    if not (p >= 1.0 or (p > 0.0 and not d.unit(_HashDraws.GATE) > p)):
+        return (0, 0, 0, 0)
+    fn = code
+    if code == 4:
+        fn = 3 if d.randint(_HashDraws.FN, 0, 1) else 2
+    elif code == 5:
+        fn = 3 if d.randint(_HashDraws.FN, 0, 1) else 1
+
+    def crop(slot_w, slot_s):
+        w = d.randint(slot_w, _ceil(n, 0.2), _ceil(n, 0.5))
+        return (2, w, d.randint(slot_s, s, e - w + 1), 0)
+
+    if n <= 1:
+        return (0, 0, 0, 0)
+    if fn == 0:
+        return (1, d.randint(_HashDraws.WIDTH, 0, nf - n), 0, 0) if n < nf else (0, 0, 0, 0)
+    if fn == 1:
+        return crop(_HashDraws.WIDTH, _HashDraws.START)
+    c = _ceil(n, 0.2)
+    if fn == 2:
+        ps, pe = s + c, e - c
+        w = d.randint(_HashDraws.WIDTH, _ceil(pe - ps, 0.2), _ceil(pe - ps, 0.5))
+        return (2, w, d.randint(_HashDraws.START, ps, pe - w + 1), 0)
+    psl, psr, pel, per = s - c, s + c, e - c, e + c
+    w = d.randint(_HashDraws.WIDTH, _ceil(pel - psr, 0.2), _ceil(pel - psr, 0.5))
+    if w <= 0:
+        return crop(_HashDraws.FB_WIDTH, _HashDraws.FB_START)
+    out_start = d.randint(_HashDraws.START, psr, pel - w + 1)
+    n_left = psl if psl >= w else 0
+    n_right = nf - w - per if nf - 1 - per >= w else 0
+    if n_left + n_right == 0:
+        return (2, w, out_start, 0)
+    k = d.randint(_HashDraws.PICK, 0, n_left + n_right - 1) if n_left + n_right > 1 else 0
+    return (3, w, out_start, k if k < n_left else per + (k - n_left))
+
+
+def augment_plans(seed, spans, nfeats, mode, aug_percentage):
+    """Host mirror of the plans ``moment_augment_device(..., plan=None, seed=seed)`` draws: int32 [B,4] numpy.  For tests and
+    for reproducing a batch (as ``cropin_positions`` is for the translate kernel)."""
+    code = aug_mode_code(mode)
+    sp = np.asarray(spans).reshape(-1, 2).tolist()
+    nf = np.asarray(nfeats).reshape(-1).tolist()
+    return np.array([_draw_plan(_HashDraws(seed, b), code, float(aug_percentage), int(s), int(e), int(n))
+                     for b, ((s, e), n) in enumerate(zip(sp, nf))], dtype=np.int32).reshape(-1, 4)
+
+
+def moment_augment_device(video, spans, nfeats, mode, aug_percentage=1.0, seed=0, plan=None):
+    """``DataAugmentForTSG.aug_data`` for a whole batch on the device, one launch (csrc/augment.hip): video [B,T,D] fp32 or bf16,
+    spans [B,2] frame stamps, nfeats [B] -> (out [B,T,D], new_spans [B,2] int32, new_nfeats [B] int32, plan [B,4] int32).
+
+    ``mode``: a reference mode name ('gt_translate', 'gt_crop', 'prot_gt_crop', 'gt_cropout', 'all') or None (gt_crop or
+    gt_cropout per sample).  Per sample the gate (applied with probability ``aug_percentage``), the candidate function and its
+    draws come from a counter-based hash of (seed, sample index); ``augment_plans`` reproduces them on the host.  ``plan``
+    [B,4] = (op, a, b, c) skips the draws: op 0 identity, 1 translate (a = cropin), 2 crop (a = width, b = start),
+    3 cropout (a = width, b = out_start, c = in_start)."""
+    from . import _lib
+    from .functional import _call
+    code = aug_mode_code(mode)
+    if plan is not None:
+        pl = np.asarray(plan.cpu() if isinstance(plan, torch.Tensor) else plan)
+        if pl.ndim != 2 or pl.shape[1] != 4 or not np.isin(pl[:, 0], (0, 1, 2, 3)).all():
+            raise ValueError(f"plan must be [B,4] with ops in 0..3, got shape {pl.shape}")
+    _lib.require_device(video)
+    dtype = {torch.float32: _lib.TSG_F32, torch.bfloat16: _lib.TSG_BF16}.get(video.dtype)
+    if dtype is None:
+        raise TypeError(f"moment_augment_device: video must be float32 or bfloat16, got {video.dtype}")
+    video = video.contiguous()
+    B, T, D = video.shape
+    sp, nf = _i32(spans, video.device), _i32(nfeats, video.device)
+    pin = _i32(plan, video.device) if plan is not None else None
+    out = torch.empty_like(video)
+    new_sp = torch.empty(B, 2, device=video.device, dtype=torch.int32)
+    new_nf = torch.empty(B, device=video.device, dtype=torch.int32)
+    pout = torch.empty(B, 4, device=video.device, dtype=torch.int32)
+    _call("tsg_moment_augment", video, video.data_ptr(), sp.data_ptr(), nf.data_ptr(), code, float(aug_percentage),
+          int(seed) & _M64, pin.data_ptr() if pin is not None else None, pout.data_ptr(), out.data_ptr(), new_sp.data_ptr(),
+          new_nf.data_ptr(), B, T, D, dtype)
+    return out, new_sp, new_nf, pout
+
+
+def augment_batch_device(batch, mode, aug_percentage, seed):
+    """A QAVE batch (``synthetic_batch`` / ``pair_batch_device`` keys) with the reference's per-sample augmentation applied
+    (charades.py:164-170, anet.py:160-161): the video, ``nfeats``, ``video_mask`` and the gt masks and ``framestps`` (through
+    ``tsg_sequence_masks``) are replaced; ``timestps`` stays as the reference leaves it.  Feeds ``engine.baseline_step``."""
+    video = batch["video"]
+    T = video.shape[1]
+    out, sp, nf, _ = moment_augment_device(video, _i32(batch["gt"]["framestps"], video.device),
+                                           _i32(batch["nfeats"], video.device), mode, aug_percentage, seed)
+    masks = sequence_masks_device(nf, sp, T)
+    new = dict(batch)
+    new["video"], new["nfeats"], new["video_mask"] = out, nf, masks.pop("video_mask")
+    new["gt"] = dict(batch["gt"], **masks)
+    new["gt"]["framestps"] = sp.long()
+    return new
