@@ -514,6 +514,36 @@ int tsg_wgrad_bf16(const void* A, long long lda, long long a_group_stride, const
  *   timestamps [B,2] double (seconds) -> framestps [B,2] = min(int(x), T-1) (charades.py:178); both NULL to skip.          */
 int tsg_pool_clips(const void* raw, const int64_t* offsets, const double* timestamps, void* out, int32_t* nfeats,
                    int32_t* framestps, int B, int T, int D, int dtype, void* stream);
+/* tsg_sample_clips: the reference datasets' six clip samplers (raw clips -> the [T, D] rows the model reads) in one kernel body;
+ *   tsg_pool_clips is its TSG_SAMPLE_PAIR mode.  raw [sum_b n_b, D] fp32 (the batch's clips back to back), offsets [B+1] int64
+ *   as tsg_pool_clips, timestamps [B,2] double seconds, durations [B] double seconds.  out [B,T,D]: row t = the mean of a window
+ *   of the sample's raw rows (a sequential fp32 sum in row order, then one correctly rounded division: np.mean over float32
+ *   rows; a window of 1 is a copy), zero rows outside the window set; dtype TSG_F32, or TSG_BF16 = that fp32 mean rounded to
+ *   nearest-even.  nfeats [B], framestps [B,2] (with timestamps; both NULL to skip, except in LG), spos_out [B] (may be NULL)
+ *   int32.  Except in LG the frame stamps are min(int(x), T-1).  D % 4 == 0, T <= 16384; TSG_E_* for an unknown mode, a
+ *   missing durations / timestamps where the mode needs them.
+ *     PAIR        charades.py:177-196   windows [2t, 2t+2) (a lone last clip copied); nfeats = min(ceil(n/2), T)
+ *     TRIPLE      charades.py:245-269   windows [3t, 3t+3) with the 2- and 1-clip tails (lgi3d); nfeats = min(ceil(n/3), T)
+ *     ONE_TO_ONE  anet.py:193-208       rows t < min(n, T) copied (ANet i3d); nfeats = min(n, T)
+ *     F2S         anet.py:173-191       rate = n / duration; row i < duration (and < T) copies clip floor(i*rate); nfeats = the
+ *                                       number of such rows  (needs durations)
+ *     F2S_114     anet.py:210-230       start = min(n-1, int(i*rate + 0.5)), end = int((i+1)*rate + 0.5); a copy of start when
+ *                                       end > n or end <= start, else the mean of [start, end); nfeats = n, NOT clamped to T
+ *     LG          charades.py:198-243,  stride = 1 if n <= T else n/T; s = rint(arange(spos, n - 0.5, stride))[:T] in numpy's
+ *                 anet.py:232-277       arange arithmetic (start, start + step, then start + i*((start+step)-start)); rows
+ *                                       feat[s[t]], nfeats = min(n, T); framestps = the s[i] <= pos < s[i+1] search over
+ *                                       pos = (n-1) * clamp(timestamp / duration, 0, 1), defaults 0 and T-1  (needs
+ *                                       durations, timestamps and framestps).  spos: the caller's spos[b] when spos is given;
+ *                                       else 0, or with train != 0 a draw from [0, int(random_end)] INCLUSIVE (random_end =
+ *                                       stride - 0.5, minus 1 when integral: np.random.random_integers) by a counter-based hash
+ *                                       of (seed, b).  spos_out receives the spos used.
+ *   Index arithmetic in double exactly as the reference forms it (no contraction).  Window starts are clamped into the sample's
+ *   rows, so inputs on which the reference raises (no clips, an arange value rounding to n) read only that sample's rows.      */
+enum { TSG_SAMPLE_PAIR = 0, TSG_SAMPLE_TRIPLE = 1, TSG_SAMPLE_ONE_TO_ONE = 2, TSG_SAMPLE_F2S = 3, TSG_SAMPLE_F2S_114 = 4,
+       TSG_SAMPLE_LG = 5 };
+int tsg_sample_clips(const void* raw, const int64_t* offsets, const double* timestamps, const double* durations, int mode,
+                     int train, uint64_t seed, const int32_t* spos, void* out, int32_t* nfeats, int32_t* framestps,
+                     int32_t* spos_out, int B, int T, int D, int dtype, void* stream);
 /* tsg_sequence_masks: Sequence_mask (charades.py:12-18: ones on [max(0,st), min(et,T-1)] INCLUSIVE) for the four masks a
  *   sample carries (charades.py:167-170, charades_pair_aug.py:96-107): video_mask = [0, nfeats], temporal_labels = [s, e],
  *   fore_mask = [0, s], back_mask = [e, nfeats].  Each output is int32 [B,T]; any of them may be NULL.                      */
@@ -521,8 +551,11 @@ int tsg_sequence_masks(const int32_t* nfeats, const int32_t* spans, int32_t* vid
                        int32_t* fore_mask, int32_t* back_mask, int B, int T, void* stream);
 /* tsg_moment_translate: the shuffling augmentation DataAugmentForTSG.gt_moment_translate (dataset/data_augment.py:135-156) as an
  *   index gather: the ground-truth moment spans[b] = [s, e] is cut out of the first nfeats[b] clips, the gap closed and the
- *   moment re-inserted in front of position cropin[b] of the gap-closed sequence; rows >= nfeats[b] become zero.  Moments of
- *   length <= 1 or covering every clip: out[b] = video[b], span unchanged.  cropin NULL: the position is drawn uniformly from
+ *   moment re-inserted in front of position cropin[b] of the gap-closed sequence; rows >= nfeats[b] become zero.  A moment
+ *   that ends at or past nfeats[b] (LG's end label T-1) leaves the gap-closed rows [0, s) only, and the output holds e+1 rows,
+ *   as the reference's does (data_augment.py:141-153); rows at or past T are never read.  Moments of
+ *   length <= 1 or covering every clip: out[b] = video[b], span unchanged.  A given cropin[b] is clamped to [0, nfeats-len],
+ *   the range the reference draws from (as tsg_moment_augment clamps its plan).  cropin NULL: the position is drawn uniformly from
  *   [0, nfeats-len] by a counter-based hash of (seed, b) (the reference: unseeded random.randint, data_augment.py:149).
  *   video, out [B,T,D] (out != video); new_spans [B,2] = [cropin, cropin+len-1].                                            */
 int tsg_moment_translate(const void* video, const int32_t* spans, const int32_t* nfeats, const int32_t* cropin,

@@ -88,6 +88,7 @@ _SIGNATURES = {
     "tsg_split_bf16x3_shift": [_P, c_longlong, c_longlong, c_longlong, _P, c_longlong, c_longlong, c_longlong, c_longlong, _I, _P],
     "tsg_split_bf16x3_t": [_P, c_longlong, c_longlong, c_longlong, _P, c_longlong, c_longlong, c_longlong, c_longlong, _I, c_longlong, _P],
     "tsg_pool_clips": [_P] * 6 + [_I] * 4 + [_P],
+    "tsg_sample_clips": [_P] * 4 + [_I, _I, c_uint64] + [_P] * 5 + [_I] * 4 + [_P],
     "tsg_sequence_masks": [_P] * 6 + [_I] * 2 + [_P],
     "tsg_moment_translate": [_P] * 4 + [c_uint64, _P, _P] + [_I] * 4 + [_P],
     "tsg_moment_augment": [_P, _P, _P, _I, ctypes.c_double, c_uint64] + [_P] * 5 + [_I] * 4 + [_P],

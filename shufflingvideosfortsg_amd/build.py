@@ -27,7 +27,9 @@ CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-W
 # per-source additions.  wgrad_split: under plain -O3 the SLP vectoriser packs the split's subtractions into v_pk_add_f32, which is slow
 # beside MFMAs (MI355X_MICROARCH.md, "price of one filler beside MFMAs"): the LSTM layer's dW 626 -> 595 us without it
 # (profiles/r4/gemm_wgrad_flags_ab_v1.txt; tsg_gemm_f32s measured the same either way and keeps the default)
-EXTRA_FLAGS = {"wgrad_split.hip": ["-fno-slp-vectorize"]}
+# input_pipeline: tsg_sample_clips keeps its index arithmetic unfused with `#pragma clang fp contract(off)` (numpy rounds
+# start + i*delta and i*rate + 0.5 in two steps); plain -ffp-contract=fast disregards that pragma
+EXTRA_FLAGS = {"wgrad_split.hip": ["-fno-slp-vectorize"], "input_pipeline.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 
 def _sources():

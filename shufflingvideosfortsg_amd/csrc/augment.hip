@@ -116,10 +116,10 @@ struct RowMap {
   __device__ __forceinline__ int src(int t) const {
     switch (op) {
       case kOpTranslate: {                                    // [0, at): gap-closed rows, [at, at+len): the moment, then the rest
-        if (t >= nf) return -1;
-        if (t >= at && t < at + len) return s + (t - at);
-        const int i = t < at ? t : t - len;
-        return i < s ? i : i + len;
+        if (t >= at && t < at + len) return s + (t - at);     // (a moment ending at or past nf: the gap-closed rows are [0, s),
+        const int i = t < at ? t : t - len;                   // as tsg_moment_translate's translate_src)
+        if (i < s) return i;
+        return i < nf - len ? i + len : -1;
       }
       case kOpCrop: return t < at ? t : t + w;                // rows [at, at+w) deleted, the rest (zero padding too) shifts left
       case kOpCropout: return t >= at && t < at + w ? from + (t - at) : t;

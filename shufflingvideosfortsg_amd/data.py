@@ -7,9 +7,14 @@ Two implementations of the same functions:
   * device (``*_device``, csrc/input_pipeline.hip through the C ABI): pair-mean pooling, the four masks and the shuffling
     augmentation for a whole batch on the GPU that consumes it, so that N ranks on one host do not queue behind numpy
     workers (the reference feeds ONE GPU from 8 DataLoader workers).  ``pair_batch_device`` assembles the GMD batch dict
-    (train.py:50-91 keys) from resident features."""
+    (train.py:50-91 keys) from resident features.
+
+The clip samplers of the reference's Charades and ActivityNet datasets (raw clip features -> the [T, D] rows the model reads)
+have numpy mirrors (``generate_video_fts_data`` ... ``lg_get_fixed_length_feat``, chosen by ``vfeat_mode``) and one device
+kernel (``sample_clips_device``, csrc/input_pipeline.hip); ``clip_batch_device`` composes it with the masks / GMD pair."""
 from __future__ import annotations
 
+import collections
 import math
 
 import numpy as np
@@ -41,7 +46,9 @@ def gt_moment_translate(framestps, nfeats, video_feat, cropin_start=None, rng=No
     order = np.concatenate([np.arange(0, s), np.arange(e + 1, nfeats)])           # gap closed
     order = np.concatenate([order[:cropin_start], np.arange(s, e + 1), order[cropin_start:]])
     out = np.zeros(video_feat.shape) + 0.0
-    out[0, :nfeats] = video_feat[0, order]
+    # nfeats rows -- or, for a moment ending at or past nfeats (LG's end label T-1), e+1 of them: the gap-closed sequence is
+    # then rows [0, s) only, and the reference's np.insert keeps every row it produced up to T (data_augment.py:141-153)
+    out[0, :len(order)] = video_feat[0, order]
     return [cropin_start, cropin_start + n - 1], nfeats, out
 
 
@@ -473,14 +480,319 @@ def moment_augment_device(video, spans, nfeats, mode, aug_percentage=1.0, seed=0
 def augment_batch_device(batch, mode, aug_percentage, seed):
     """A QAVE batch (``synthetic_batch`` / ``pair_batch_device`` keys) with the reference's per-sample augmentation applied
     (charades.py:164-170, anet.py:160-161): the video, ``nfeats``, ``video_mask`` and the gt masks and ``framestps`` (through
-    ``tsg_sequence_masks``) are replaced; ``timestps`` stays as the reference leaves it.  Feeds ``engine.baseline_step``."""
+    ``tsg_sequence_masks``) are replaced; ``timestps`` stays as the reference leaves it.  Feeds ``engine.baseline_step``.
+
+    nfeats > T (``sample_clips_device`` mode 'f2s_114' returns the clip count itself): the augmentation works on the T rows there
+    are -- it gets min(nfeats, T), so every draw and every row it moves lies inside the video -- and the returned nfeats follows
+    the reference's arithmetic on the full count (a crop subtracts its width, the other ops keep it).  The masks are the
+    reference's wherever it does not raise: Sequence_mask clamps to T - 1.  For nfeats <= T this is the plain call."""
     video = batch["video"]
     T = video.shape[1]
-    out, sp, nf, _ = moment_augment_device(video, _i32(batch["gt"]["framestps"], video.device),
-                                           _i32(batch["nfeats"], video.device), mode, aug_percentage, seed)
+    nf_full = _i32(batch["nfeats"], video.device)
+    nf_in = torch.clamp(nf_full, max=T)
+    out, sp, nf, _ = moment_augment_device(video, _i32(batch["gt"]["framestps"], video.device), nf_in, mode, aug_percentage,
+                                           seed)
+    nf = nf + (nf_full - nf_in)
     masks = sequence_masks_device(nf, sp, T)
     new = dict(batch)
     new["video"], new["nfeats"], new["video_mask"] = out, nf, masks.pop("video_mask")
     new["gt"] = dict(batch["gt"], **masks)
     new["gt"]["framestps"] = sp.long()
     return new
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# clip-feature sampling: the reference datasets' six samplers (raw clips -> [T, D] rows), numpy mirrors and the device
+# kernel (csrc/input_pipeline.hip: tsg_sample_clips)
+# ---------------------------------------------------------------------------------------------------------------------
+
+# sampler names -> TSG_SAMPLE_* of include/tsg_hip.h
+SAMPLE_MODES = {"pair": 0, "triple": 1, "1to1": 2, "f2s": 3, "f2s_114": 4, "lg": 5}
+FRAME2SEC_RULES = ("identity", "lg", "unsupported")
+
+
+def _framestamps(timestamps, T):
+    """int(x) if int(x) < SAMPLE_LEN else SAMPLE_LEN - 1 (charades.py:178, anet.py:174)."""
+    return [int(x) if int(x) < T else T - 1 for x in timestamps]
+
+
+def generate_video_fts_data(video_fts, timestamps, T):
+    """Charades' default sampler (generate_video_fts_data, charades.py:177-196): the mean of clips 2j, 2j+1 (np.mean over float32
+    rows), a lone last clip copied, at most T rows.  -> (video [T,D] float64, framestamps, nfeats)."""
+    n, D = np.shape(video_fts)
+    out = np.zeros([T, D]) + 0.0
+    add = 0
+    for i in range(0, n, 2):
+        out[add] = np.mean(video_fts[i:i + 2, :], 0) if i + 1 <= n - 1 else video_fts[i, :]
+        add += 1
+        if add == T:
+            break
+    return out, _framestamps(timestamps, T), add
+
+
+def lg_generate_video_fts_data(video_fts, timestamps, T):
+    """Charades lgi3d (lg_generate_video_fts_data, charades.py:245-269): the mean of clips 3j..3j+2, with the 2- and 1-clip
+    tails.  -> (video [T,D], framestamps, nfeats)."""
+    n, D = np.shape(video_fts)
+    out = np.zeros([T, D]) + 0.0
+    add = 0
+    for i in range(0, n, 3):
+        out[add] = np.mean(video_fts[i:i + 3, :], 0) if i + 1 <= n - 1 else video_fts[i, :]
+        add += 1
+        if add == T:
+            break
+    return out, _framestamps(timestamps, T), add
+
+
+def sample_1to1_video_feat(video_fts, timestamps, T):
+    """ANet i3d (sample_1to1_video_feat, anet.py:193-208): the first min(n, T) clips.  -> (video [T,D], framestamps, nfeats)."""
+    n, D = np.shape(video_fts)
+    out = np.zeros([T, D]) + 0.0
+    add = min(n, T)
+    out[:add] = video_fts[:add, :]
+    return out, _framestamps(timestamps, T), add
+
+
+def _f2s_rows(duration, T):
+    """The output rows the frame2second samplers fill: i < duration and i < T (anet.py:185-186, :221-222)."""
+    return [i for i in range(T) if i < duration]
+
+
+def sample_frame2second(video_fts, timestamps, duration, T):
+    """ANet c3d 'raw' (sample_frame2second, anet.py:173-191): rate = n / duration; row i < duration (and < T) is clip
+    floor(i * rate).  -> (video [T,D], framestamps, nfeats = the number of such rows)."""
+    n, D = np.shape(video_fts)
+    rate = n / duration
+    rows = _f2s_rows(duration, T)
+    out = np.zeros([T, D])
+    out[rows] = video_fts[[max(0, math.floor(i * rate)) for i in rows]]
+    return out, _framestamps(timestamps, T), len(rows)
+
+
+def _f2s_114_window(i, n, rate):
+    """[start, end) of row i of sample_frame2second_114 (anet.py:223-228); a window of one clip where it copies."""
+    start = min(n - 1, max(0, int(i * rate + 0.5)))
+    end = int((i + 1) * rate + 0.5)
+    return (start, start + 1) if end > n or end <= start else (start, end)
+
+
+def sample_frame2second_114(video_fts, timestamps, duration, T):
+    """ANet c3d '114' and any unknown name (sample_frame2second_114, anet.py:210-230): row i < duration (and < T) is the mean of
+    clips [start, end) with start = min(n-1, int(i*rate + 0.5)), end = int((i+1)*rate + 0.5), or a copy of clip start when
+    end > n or end <= start.  -> (video [T,D], framestamps, nfeats = n -- NOT clamped to T, as the reference returns it)."""
+    n, D = np.shape(video_fts)
+    rate = n / duration
+    out = np.zeros([T, D])
+    for i in _f2s_rows(duration, T):
+        lo, hi = _f2s_114_window(i, n, rate)
+        out[i] = video_fts[lo] if hi - lo == 1 else np.mean(video_fts[lo:hi, :], 0)
+    return out, _framestamps(timestamps, T), n
+
+
+def lg_spos_range(n, T):
+    """The inclusive range [0, hi] of LG's training start position: the reference draws np.random.random_integers(0, r) with
+    r = stride - 0.5, lowered by 1 when integral, and random_integers draws from [0, int(r)] (charades.py:209-215,
+    anet.py:243-249).  n <= T (stride 1): [0, 0]."""
+    stride = n / T if n > T else 1.0
+    r = stride - 0.5
+    return 0, int(r - 1.0 if r == math.floor(r) else r)
+
+
+def lg_positions(n, T, spos):
+    """The clips LG samples (charades.py:216-225, anet.py:250-259): rint of np.arange(spos, n - 0.5, stride), at most T of them.
+    np.arange itself forms the values (start, start + step, then start + i*((start + step) - start)); min(n, T) entries on
+    every input the reference accepts."""
+    stride = n * 1.0 / T if n > T else 1
+    return np.round(np.arange(spos, n - 0.5, stride)).astype(int)[:T]
+
+
+def _lg_label(s, pos, default):
+    """The i with s[i] <= pos < s[i+1] (the last such i; the positions are increasing, so there is at most one), else default."""
+    hits = [i for i in range(len(s) - 1) if s[i] <= pos < s[i + 1]]
+    return hits[-1] if hits else default
+
+
+def lg_get_fixed_length_feat(feat, timestamps, duration, T, spos=0):
+    """vfeat_fn 'lg' (lg_get_fixed_length_feat, charades.py:198-243 = anet.py:232-277) with the start position ``spos`` given
+    (the reference: 0 outside training, a draw over ``lg_spos_range`` in training).  Rows feat[s[t]] for s = ``lg_positions``;
+    the labels are the ``_lg_label`` of (n - 1) * clamp(timestamp / duration, 0, 1), defaults 0 and T - 1.
+    -> (video [T,D], (start_index, end_index), nfeats = min(n, T))."""
+    n = feat.shape[0]
+    s = lg_positions(n, T, spos)
+    ps, pe = (float(n - 1.0) * min(max(x / duration, 0), 1) for x in timestamps[:2])
+    out = np.zeros((T, feat.shape[1]))
+    out[:len(s)] = feat[s]
+    return out, (_lg_label(s, ps, 0), _lg_label(s, pe, T - 1)), min(n, T)
+
+
+VfeatMode = collections.namedtuple("VfeatMode", "sampler frame2sec")
+
+
+def vfeat_mode(dataset, feature_type, vfeat_fn):
+    """The reference's choice of sampler and of frame2sec rule from (dataset, feature_type, vfeat_fn) -> VfeatMode(sampler,
+    frame2sec), sampler in SAMPLE_MODES, frame2sec in FRAME2SEC_RULES.
+
+    Charades (charades.py:101-107, :275-279): vfeat_fn.lower() == 'lg' -> 'lg'; else feature_type 'lgi3d' -> 'triple'; else
+    'pair'.  frame2sec converts only when vfeat_fn is exactly 'lg' (an 'LG' samples as lg but keeps frame indices).
+    ActivityNet (anet.py:66-79, :283-289): feature_type 'i3d' -> '1to1' whatever vfeat_fn says; else 'raw' -> 'f2s', '114' ->
+    'f2s_114', 'lg' -> 'lg', any other name -> 'f2s_114' (and the name becomes '114').  frame2sec keys on the NAME: ANet i3d
+    with vfeat_fn 'lg' samples 1:1 but converts as lg; ANet i3d with an unknown name samples 1:1 and its frame2sec raises
+    ('unsupported')."""
+    ds = str(dataset).lower()
+    if ds.startswith("charades"):
+        if vfeat_fn.lower() == "lg":
+            sampler = "lg"
+        elif feature_type.lower() in ["lgi3d"]:
+            sampler = "triple"
+        else:
+            sampler = "pair"
+        return VfeatMode(sampler, "lg" if vfeat_fn in ["lg"] else "identity")
+    if ds.startswith("anet") or ds.startswith("activitynet"):
+        name = vfeat_fn
+        if feature_type in ["i3d"]:
+            sampler = "1to1"
+        elif vfeat_fn in ["raw"]:
+            sampler = "f2s"
+        elif vfeat_fn in ["114"]:
+            sampler = "f2s_114"
+        elif vfeat_fn in ["lg"]:
+            sampler = "lg"
+        else:
+            name, sampler = "114", "f2s_114"
+        rule = "identity" if name in ["raw", "114"] else ("lg" if name in ["lg"] else "unsupported")
+        return VfeatMode(sampler, rule)
+    raise ValueError(f"unknown dataset {dataset!r}: expected Charades or ActivityNet")
+
+
+def sample_clips_numpy(video_fts, timestamps, duration, T, mode, spos=0):
+    """One sample through the numpy mirror of ``mode`` (a SAMPLE_MODES name) -> (video [T,D], framestps, nfeats)."""
+    if mode == "pair":
+        return generate_video_fts_data(video_fts, timestamps, T)
+    if mode == "triple":
+        return lg_generate_video_fts_data(video_fts, timestamps, T)
+    if mode == "1to1":
+        return sample_1to1_video_feat(video_fts, timestamps, T)
+    if mode == "f2s":
+        return sample_frame2second(video_fts, timestamps, duration, T)
+    if mode == "f2s_114":
+        return sample_frame2second_114(video_fts, timestamps, duration, T)
+    if mode == "lg":
+        return lg_get_fixed_length_feat(video_fts, timestamps, duration, T, spos)
+    raise ValueError(f"unknown sampling mode {mode!r}; expected one of {sorted(SAMPLE_MODES)}")
+
+
+def lg_spos_draws(seed, n_clips, T):
+    """Host mirror of the device's LG training draws (``sample_clips_device(..., mode='lg', train=True, seed=seed)``): per sample
+    a counter-based hash of (seed, b) mapped by multiply-high onto the inclusive range of ``lg_spos_range``.  int32 [B]."""
+    out = []
+    for b, n in enumerate(np.asarray(n_clips).reshape(-1).tolist()):
+        _, hi = lg_spos_range(int(n), int(T))
+        if hi <= 0:
+            out.append(0)
+            continue
+        h = _splitmix64((int(seed) & _M64) ^ ((0xD1B54A32D192ED03 * (b + 1)) & _M64) ^ 0x8CB92BA72F3D8DD7)
+        out.append(((h >> 32) * (hi + 1)) >> 32)
+    return np.array(out, dtype=np.int32)
+
+
+def sample_code(mode):
+    if isinstance(mode, str) and mode in SAMPLE_MODES:
+        return SAMPLE_MODES[mode]
+    raise ValueError(f"unknown sampling mode {mode!r}; expected one of {sorted(SAMPLE_MODES)}")
+
+
+def sample_clips_device(raw, offsets, T, mode, timestamps=None, durations=None, train=False, seed=0, spos=None,
+                        out_dtype=torch.float32):
+    """The reference's per-sample sampler for a whole batch in one launch (tsg_sample_clips): ``raw`` [sum n_b, D] fp32 device
+    tensor (the batch's clips back to back), ``offsets`` [B+1], ``mode`` a SAMPLE_MODES name, ``timestamps`` [B,2] seconds,
+    ``durations`` [B] seconds ('f2s', 'f2s_114', 'lg' need them; 'lg' needs timestamps).  'lg' draws its start position per
+    sample in training (``train``; host mirror: ``lg_spos_draws``) unless ``spos`` [B] is given; 0 otherwise.
+    -> (video [B,T,D] ``out_dtype`` (float32, or bfloat16 = the fp32 rows rounded to nearest-even), nfeats [B] int32,
+    framestps [B,2] int32 or None without timestamps, spos [B] int32: the start positions used, 0 outside 'lg')."""
+    from . import _lib
+    from .functional import _call
+    code = sample_code(mode)
+    dt = {torch.float32: _lib.TSG_F32, torch.bfloat16: _lib.TSG_BF16}.get(out_dtype)
+    if dt is None:
+        raise TypeError(f"sample_clips_device: out_dtype must be float32 or bfloat16, got {out_dtype}")
+    if mode in ("f2s", "f2s_114", "lg") and durations is None:
+        raise ValueError(f"sampling mode {mode!r} needs durations")
+    if mode == "lg" and timestamps is None:
+        raise ValueError("sampling mode 'lg' needs timestamps")
+    _lib.require_device(raw)
+    if raw.dtype != torch.float32 or raw.dim() != 2:
+        raise TypeError(f"sample_clips_device: raw must be a [sum n, D] float32 tensor, got {raw.dtype} {tuple(raw.shape)}")
+    raw = raw.contiguous()
+    dev = raw.device
+    off = torch.as_tensor(offsets, device=dev).to(torch.int64).contiguous()
+    B, D = off.numel() - 1, raw.shape[1]
+    out = torch.empty(B, T, D, device=dev, dtype=out_dtype)
+    nf = torch.empty(B, device=dev, dtype=torch.int32)
+    sp_out = torch.empty(B, device=dev, dtype=torch.int32)
+    ts = fs = du = sp_in = None
+    if timestamps is not None:
+        ts = torch.as_tensor(timestamps, device=dev).to(torch.float64).reshape(B, 2).contiguous()
+        fs = torch.empty(B, 2, device=dev, dtype=torch.int32)
+    if durations is not None:
+        du = torch.as_tensor(durations, device=dev).to(torch.float64).reshape(B).contiguous()
+    if spos is not None:
+        sp_in = _i32(spos, dev).reshape(B)
+
+    def p(t):
+        return t.data_ptr() if t is not None else None
+    _call("tsg_sample_clips", raw, raw.data_ptr(), off.data_ptr(), p(ts), p(du), code, int(bool(train)), int(seed) & _M64,
+          p(sp_in), out.data_ptr(), nf.data_ptr(), p(fs), sp_out.data_ptr(), B, T, D, dt)
+    return out, nf, fs, sp_out
+
+
+def frame2sec(pred, durations, nfeats, rule):
+    """The datasets' frame2sec on a batch of predicted [start, end] frame indices (charades.py:271-279, anet.py:279-289).
+    'identity': returned as given; 'lg': _lg_frame2sec = pred / nfeats[:, None] * durations[:, None], on tensors with the
+    dtypes of the reference's collate_fn and test loop (pred float32, durations float64, nfeats int64): the quotient is
+    float32, the result float64; 'unsupported': NotImplementedError, as the reference's ANet frame2sec raises."""
+    if rule == "identity":
+        return pred
+    if rule == "unsupported":
+        raise NotImplementedError("frame2sec: the reference has no rule for this vfeat_fn")
+    if rule != "lg":
+        raise ValueError(f"unknown frame2sec rule {rule!r}; expected one of {FRAME2SEC_RULES}")
+    pred = torch.as_tensor(pred).float()
+    dur = durations if isinstance(durations, torch.Tensor) else torch.from_numpy(np.array(durations, dtype=np.float64))
+    nf = nfeats if isinstance(nfeats, torch.Tensor) else torch.from_numpy(np.array(nfeats, dtype=np.int64))
+    pos = pred / nf.to(pred.device).unsqueeze(1)
+    return pos * dur.to(pred.device).unsqueeze(1)
+
+
+def clip_batch_device(raw, offsets, T, mode, query, timestamps, durations=None, train=False, seed=0, spos=None, pair=False,
+                      cropin_start=None, out_dtype=torch.float32, aug=None):
+    """One batch from raw clip features on the device: ``sample_clips_device`` then the QAVE masks (``pair=False``: the keys of
+    ``synthetic_batch``; ``aug`` = (aug_mode, aug_percentage) applies the trainers' augmentation through
+    ``augment_batch_device`` with ``seed``) or the GMD pair (``pair=True``: ``pair_batch_device``, shuffled with the insert
+    positions ``cropin_start`` or drawn from ``seed``; fp32 only).  query [B,N,300] device tensor.
+
+    nfeats > T: 'f2s_114' returns clip counts above T (the reference's collate passes them on, and its shuffling augmentation
+    raises on them).  The masks, the GMD shuffle and the augmentation get min(nfeats, T) -- Sequence_mask clamps to T - 1, so
+    the masks are the reference's -- and batch['nfeats'] is the count as the reference computes it (``augment_batch_device``
+    holds the same rule for the QAVE augmentation).  Adds 'durations' (float64) and gt 'timestps' (float32, as collate_fn)
+    for ``engine.evaluate`` / ``frame2sec``."""
+    if pair and aug is not None:
+        raise ValueError("clip_batch_device: the GMD pair carries its own shuffle; aug applies to QAVE batches (pair=False)")
+    dev = raw.device
+    video, nf, fs, sp = sample_clips_device(raw, offsets, T, mode, timestamps, durations, train, seed, spos, out_dtype)
+    nf_c = torch.clamp(nf, max=T)
+    ts = torch.as_tensor(timestamps).to(torch.float64).reshape(-1, 2).float().to(dev)
+    if pair:
+        if out_dtype != torch.float32:
+            raise TypeError("clip_batch_device: the GMD pair is built in float32")
+        batch = pair_batch_device(video, nf_c, fs, query, seed=seed, cropin_start=cropin_start, timestps=ts)
+    else:
+        m = sequence_masks_device(nf_c, fs, T)
+        batch = {"video": video, "query": query, "video_mask": m.pop("video_mask"),
+                 "query_mask": torch.ones(query.shape[0], query.shape[1], dtype=torch.int32, device=dev), "gt": m}
+        batch["gt"]["framestps"], batch["gt"]["timestps"] = fs.long(), ts
+    batch["nfeats"], batch["spos"] = nf, sp
+    if aug is not None:
+        batch = augment_batch_device(batch, aug[0], aug[1], seed)
+    if durations is not None:
+        batch["durations"] = torch.as_tensor(durations).to(torch.float64).reshape(-1).to(dev)
+    return batch

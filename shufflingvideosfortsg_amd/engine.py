@@ -386,10 +386,15 @@ def gmd_step(model, batch, params):
 
 
 @torch.no_grad()
-def evaluate(model, batches: Iterable[Dict], params: Dict = None) -> Dict:
+def evaluate(model, batches: Iterable[Dict], params: Dict = None, vfeat_mode=None) -> Dict:
     """-> submits dict {'version','results','external_data','params'} (test_baseline.py:86-137).
     Each batch may carry 'sentences', 'vids', 'durations' lists; predicted 'seconds' are frame indices
-    (frame2sec is the identity for raw features, charades.py:275-279)."""
+    (frame2sec is the identity for raw features, charades.py:275-279).
+    ``vfeat_mode``: a frame2sec rule of ``data.frame2sec`` ('identity', 'lg') or a ``data.vfeat_mode`` result; the predictions
+    then go through the dataset's frame2sec (test.py:117) with the batch's 'nfeats' and 'durations' -- 'lg' converts frame
+    indices to seconds (_lg_frame2sec, charades.py:271-273).  None: frame indices, as before."""
+    from . import data as _data
+    rule = getattr(vfeat_mode, "frame2sec", vfeat_mode)
     model.eval()
     sub = {"version": "V0", "results": {}, "external_data": {"used": True, "details": "provided i3D feature"},
            "params": params or {}}
@@ -397,7 +402,11 @@ def evaluate(model, batches: Iterable[Dict], params: Dict = None) -> Dict:
         fwd = model.eval_forward if isinstance(model, GMD) else model
         out = fwd(batch["video"], batch["query"], batch["video_mask"], batch["query_mask"])
         pred, score = L.span_pred(out["start"], out["end"])
-        pred, score = pred.float().cpu().numpy(), score.cpu().numpy()
+        pred = pred.float()
+        if rule is not None and rule != "identity":
+            pred = _data.frame2sec(pred.cpu(), torch.as_tensor(batch["durations"]).cpu().to(torch.float64),
+                                   torch.as_tensor(batch["nfeats"]).cpu().to(torch.int64), rule)
+        pred, score = pred.cpu().numpy(), score.cpu().numpy()
         B = pred.shape[0]
         ts = batch["gt"]["timestps"].cpu().numpy()
         for i in range(B):
