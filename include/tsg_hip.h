@@ -26,7 +26,8 @@
  *     tsg_lstm_set_persist (initialised from TSG_LSTM_L2X / TSG_LSTM_PERSIST in the environment on first use).
  *   - results are bitwise reproducible run to run except the sums formed with float atomics: dw of K1, dgbias of K1g, dcs / dw2 /
  *     db2 of K5, the K4 loss accumulators, the LSTM's dbias (one atomic add per batch slice and column), dcs / db1 / dw2 of K3, and
- *     dK / dV of tsg_mha_bwd with TSG_F32S when Tk <= 32 and Tq > 128 (one atomic add per query block).
+ *     dK / dV of tsg_mha_bwd with TSG_F32S when Tk <= 32 and Tq > 128 (one atomic add per query block), and dw of tsg_scdm_long_bwd /
+ *     dw and dgbias of tsg_scdm_long_gate_bwd (one atomic add per column and workgroup; their other outputs are written exactly once).
  */
 #ifndef TSG_HIP_H
 #define TSG_HIP_H
@@ -44,7 +45,8 @@ extern "C" {
                               environment variable and an error code); per-device error words
                            6: tsg_lstm_fwd_ws (the persistent LSTM forward's exchange ring in a caller-owned workspace), tsg_gemm_bf16, tsg_adam_step,
                               tsg_gemm_f32s_nn_acc, tsg_lstm_set_ring / _wide, tsg_wgrad_set_stream_k
-                           7: tsg_time_next_launch / tsg_timed_launch_us (one launch bracketed by its own event pair), tsg_grads_nonfinite */
+                           7: tsg_time_next_launch / tsg_timed_launch_us (one launch bracketed by its own event pair), tsg_grads_nonfinite;
+                              tsg_scdm_long_* (K1 / K1g for sentences of up to tsg_scdm_long_max_words() words) added without a new revision */
 #define TSG_F32 0
 #define TSG_BF16 1   /* bf16 storage of the activations, fp32 arithmetic (see Conventions)                               */
 #define TSG_F32S 2   /* fp32 storage; matrix products as split-precision bf16 MFMAs (x = hi + lo; hi*hi + hi*lo + lo*hi,
@@ -73,8 +75,8 @@ int tsg_timed_launch_us(int slot, float* us);
  * inputs are the PROJECTED tensors: a = W_a(video)+b [B,T,H], s = W_s(sent) [B,N,H], w [H] (the
  * [1,H] weight of self.w), sent [B,N,Ds].  Computes, without ever materialising [B,T,N,H]:
  *   e[b,t,n] = sum_k w[k]*tanh(a[b,t,k]+s[b,n,k]);  P = softmax_n(e);  C = P @ sent.
- * Outputs C [B,T,Ds] and P [B,T,N] (kept for the backward).  Limits: N <= 32, H%4==0, Ds%4==0,
- * roundup(N,4)*roundup(H,256)*4 B must fit LDS (TSG_E_LDS otherwise).
+ * Outputs C [B,T,Ds] and P [B,T,N] (kept for the backward).  Limits: N <= 32 (longer sentences: tsg_scdm_long_* below),
+ * H%4==0, Ds%4==0, roundup(N,4)*roundup(H,256)*4 B must fit LDS (TSG_E_LDS otherwise).
  * dtype TSG_F32S: C = P @ sent as split-precision bf16 MFMA products where H == Ds in {256, 512, 1024} (else as TSG_F32).
  * dtype TSG_BF16: a, s, sent, C (and dC, da, ds, dsent in the backward) are bf16; w, P, dw stay fp32.                  */
 int tsg_scdm_attn_fwd(const void* a, const void* s, const void* w, const void* sent,
@@ -116,6 +118,32 @@ int tsg_scdm_gate_bwd(const void* a, const void* s, const void* w, const void* V
                       const void* r, const void* P, const void* dout, void* da, void* ds, void* dw,
                       void* dVW, void* dgbias, void* dr, void* ws, long long ws_bytes,
                       int B, int T, int N, int H, int Ds, int dtype, void* stream);
+
+/* ---- K1L: K1 and K1g for long sentences.  The same mathematics, operands and dtypes as tsg_scdm_attn_* / tsg_scdm_gate_* with the
+ * words walked in chunks of 16, so N is limited by tsg_scdm_long_max_words() (128) and not by LDS or registers.
+ * Limits: 1 <= N <= 128 (N <= 32 is accepted too), H % 4 == 0, Ds % 4 == 0, H <= 1024, Ds <= 1024, B * T < 2^31; beyond them
+ * TSG_E_SHAPE / TSG_E_ALIGN with a message naming the dimension.  Every argument check runs before any launch.
+ * a and s are clamped to +-40 each in the product form exp(2a) exp(2s); where an operand itself lies beyond +-40 the kernels compute
+ * tanh from the clamped SUM a + s instead, so the result is exact at any magnitude.
+ * dtype: TSG_F32; TSG_F32S computes exactly as TSG_F32; TSG_BF16 = a, s, sent / VW, r, C / out and their gradients are bf16, while
+ * w, gbias, P, dw, dgbias stay fp32.
+ * Forward: one launch, no scratch.  Backward: five launches on `stream` (rows: de [and dr, dz]; da; ds + dw, in two launches that split the workgroups; dsent / dVW + dgbias), no
+ * exchange between workgroups and no co-residency requirement.  da, ds, dsent / dVW and dr are written exactly once, without atomics;
+ * dw and dgbias are zeroed by the call and summed with float atomics (one add per column and workgroup).
+ * `ws`: caller-owned workspace of at least tsg_scdm_long_ws_bytes(B,T,N,H,Ds,gate) bytes (de [B*T][roundup(N,4)] fp32, then, gate = 1,
+ * dz [B*T][Ds] fp32), contents irrelevant; the function returns 0 for shapes the entry points reject.                          */
+int       tsg_scdm_long_max_words(void);
+long long tsg_scdm_long_ws_bytes(int B, int T, int N, int H, int Ds, int gate);
+int tsg_scdm_long_fwd(const void* a, const void* s, const void* w, const void* sent, void* C, void* P,
+                      int B, int T, int N, int H, int Ds, int dtype, void* stream);
+int tsg_scdm_long_bwd(const void* a, const void* s, const void* w, const void* sent, const void* P, const void* dC,
+                      void* da, void* ds, void* dw, void* dsent, void* ws, long long ws_bytes,
+                      int B, int T, int N, int H, int Ds, int dtype, void* stream);
+int tsg_scdm_long_gate_fwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias, const void* r,
+                           void* out, void* P, int B, int T, int N, int H, int Ds, int dtype, void* stream);
+int tsg_scdm_long_gate_bwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias, const void* r,
+                           const void* P, const void* dout, void* da, void* ds, void* dw, void* dVW, void* dgbias, void* dr,
+                           void* ws, long long ws_bytes, int B, int T, int N, int H, int Ds, int dtype, void* stream);
 
 /* ---- K3: boundary-score head (VideoSentenceConcat + MLP_predictor.forward,
  * components/CrossModalInteraction.py:44-47 + components/SpanPredictor.py:71-85; GMD gate

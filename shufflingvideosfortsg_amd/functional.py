@@ -781,6 +781,119 @@ def scdm_gate_proj(x, wa, s, w, VW, gbias):
     return _ScdmGateProj.apply(x, wa, s, w.reshape(-1), VW, gbias)
 
 
+def scdm_long_max_words() -> int:
+    """Largest sentence length the long-sentence kernels take (tsg_scdm_long_max_words)."""
+    return int(load().tsg_scdm_long_max_words())
+
+
+def scdm_long_ok(N: int, H: int, Ds: int) -> bool:
+    """Shapes ``scdm_attn_long`` / ``scdm_gate_long`` take, in every storage dtype (the library's own planner, not a failing call)."""
+    return int(load().tsg_scdm_long_ws_bytes(1, 1, N, H, Ds, 1)) > 0
+
+
+def _long_dtype(bf: bool) -> int:
+    return TSG_BF16 if bf else (TSG_F32S if _GEMM_DTYPE == "f32s" else TSG_F32)
+
+
+def _long_check(what: str, N: int, H: int, Ds: int) -> None:
+    nmax = scdm_long_max_words()
+    if N > nmax:
+        raise RuntimeError(f"{what}: N={N} words > {nmax}, the limit of the long-sentence kernels (tsg_scdm_long_max_words)")
+
+
+class _ScdmAttnLong(torch.autograd.Function):
+    """K1 for up to 128 words (tsg_scdm_long_*): (a=[B,T,H], s=[B,N,H], w=[H], sent=[B,N,Ds]) -> (C=[B,T,Ds], P=[B,T,N]).
+    The bf16 kernels take every shape the fp32 ones take, so no shape goes through fp32 copies; the backward's five launches
+    exchange nothing between workgroups, so no co-residency gate is asked for."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, a, s, w, sent):
+        require_device(a, s, w, sent)
+        bf = a.dtype == _BF
+        a, s, w, sent = _act(a, bf), _act(s, bf), _f32p(w), _act(sent, bf)
+        B, T, H = a.shape
+        _, N, Ds = sent.shape
+        if s.shape != (B, N, H) or w.numel() != H:
+            raise ValueError(f"scdm_attn_long: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} w{tuple(w.shape)} sent{tuple(sent.shape)}")
+        _long_check("scdm_attn_long", N, H, Ds)
+        C = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
+        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
+        ctx.dt = _long_dtype(bf)
+        _call("tsg_scdm_long_fwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(C), ptr(P), B, T, N, H, Ds, ctx.dt)
+        ctx.save_for_backward(a, s, w, sent, P)
+        ctx.mark_non_differentiable(P)
+        return C, P
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, dC, _dP):
+        a, s, w, sent, P = ctx.saved_tensors
+        dC = _act(dC, ctx.dt == TSG_BF16)
+        B, T, H = a.shape
+        _, N, Ds = sent.shape
+        da = torch.empty_like(a); ds = torch.empty_like(s)
+        dw = torch.empty_like(w); dsent = torch.empty_like(sent)
+        nb = int(load().tsg_scdm_long_ws_bytes(B, T, N, H, Ds, 0))
+        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
+        _call("tsg_scdm_long_bwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(P), ptr(dC), ptr(da), ptr(ds),
+              ptr(dw), ptr(dsent), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
+        return da, ds, dw, dsent
+
+
+def scdm_attn_long(a, s, w, sent, return_p: bool = False):
+    """``scdm_attn`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
+    C, P = _ScdmAttnLong.apply(a, s, w.reshape(-1), sent)
+    return (C, P) if return_p else C
+
+
+class _ScdmGateLong(torch.autograd.Function):
+    """K1g for up to 128 words: (a, s, w, VW=[B,N,Ds], gbias=[Ds], r=[B,T,Ds]) -> out = r * sigmoid(P @ VW + gbias)."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, a, s, w, VW, gbias, r, sink=None):
+        require_device(a, s, w, VW, gbias, r)
+        ctx.sink, ctx.r_in = sink, (r if sink is not None else None)
+        bf = r.dtype == _BF
+        a, s, w, VW, gbias, r = _act(a, bf), _act(s, bf), _f32p(w), _act(VW, bf), _f32p(gbias), _act(r, bf)
+        B, T, H = a.shape
+        _, N, Ds = VW.shape
+        if s.shape != (B, N, H) or w.numel() != H or r.shape != (B, T, Ds) or gbias.numel() != Ds:
+            raise ValueError(f"scdm_gate_long: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} VW{tuple(VW.shape)} r{tuple(r.shape)}")
+        _long_check("scdm_gate_long", N, H, Ds)
+        out = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
+        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
+        ctx.dt = _long_dtype(bf)
+        _call("tsg_scdm_long_gate_fwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(out), ptr(P),
+              B, T, N, H, Ds, ctx.dt)
+        ctx.save_for_backward(a, s, w, VW, gbias, r, P)
+        return out
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, dout):
+        a, s, w, VW, gbias, r, P = ctx.saved_tensors
+        dout = _act(dout, ctx.dt == TSG_BF16)
+        B, T, H = a.shape
+        _, N, Ds = VW.shape
+        da = torch.empty_like(a); ds = torch.empty_like(s); dw = torch.empty_like(w)
+        dVW = torch.empty_like(VW); dgb = torch.empty_like(gbias); dr = torch.empty_like(r)
+        nb = int(load().tsg_scdm_long_ws_bytes(B, T, N, H, Ds, 1))
+        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
+        _call("tsg_scdm_long_gate_bwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(P), ptr(dout),
+              ptr(da), ptr(ds), ptr(dw), ptr(dVW), ptr(dgb), ptr(dr), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
+        if ctx.sink is not None and ctx.sink.tensor is not None and dr.dtype == ctx.sink.tensor.dtype:
+            _sink_add(ctx.sink, ctx.r_in, dr)                  # r is a shared activation: its gradient meets W_a's there, as in _ScdmGate
+            dr = None
+        return da, ds, dw, dVW, dgb, dr, None
+
+
+def scdm_gate_long(a, s, w, VW, gbias, r):
+    """``scdm_gate`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
+    return _ScdmGateLong.apply(a, s, w.reshape(-1), VW, gbias, r, _sink_for(r))
+
+
 _k3_ws = {}        # (device, stream, B, T, Hm) -> uint8 workspace of the one-launch K3 backward; its ticket counters are zero between calls
 
 

@@ -120,6 +120,8 @@ class SCDM_Attention(nn.Module):
 
     def forward(self, video_feat, sent_feat):
         a, s = self.projections(video_feat, sent_feat)
+        if sent_feat.size(1) > 32:                               # K1 stops at 32 words: the chunked kernels (K1L) from there on
+            return TF.scdm_attn_long(a, s, self.w.weight, sent_feat)
         return TF.scdm_attn(a, s, self.w.weight, sent_feat)
 
     def projections(self, video_feat, sent_feat):
