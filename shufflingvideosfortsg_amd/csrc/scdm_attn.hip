@@ -35,6 +35,7 @@
 #include "tsg_common.h"
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 #include <type_traits>
 
@@ -2101,108 +2102,120 @@ __global__ void zero3_kernel(unsigned* p0, int n0, unsigned* p1, int n1, unsigne
 // host-side dispatch
 // ------------------------------------------------------------------------------------------
 
-template <int NP, bool GATE, typename ST>
-int launch_fwd(const ST* a, const ST* s, const float* w, const ST* V, ST* C, float* P,
-               const ST* gr, const float* gbias, int B, int T, int N, int H, int Ds, hipStream_t st) {
-  constexpr int R = 1;                       // clip rows per wave and sub-tile (sub-tile = 8R rows)
-  constexpr int SUB = kFwdWaves * R;
-  // rows per workgroup: as many as still give every CU a workgroup (the Es prologue, the launch ramp and the store
-  // tail are paid once per workgroup: 64 rows at 128 pairs x 128 clips measured 80 us vs 88 us for 32-row groups)
+#define TSG_DISPATCH_NP(NPV, CALL)                                  \
+  switch (NPV) {                                                    \
+    case 4: { constexpr int NP = 4; return CALL; }                  \
+    case 8: { constexpr int NP = 8; return CALL; }                  \
+    case 12: { constexpr int NP = 12; return CALL; }                \
+    case 16: { constexpr int NP = 16; return CALL; }                \
+    case 20: { constexpr int NP = 20; return CALL; }                \
+    case 24: { constexpr int NP = 24; return CALL; }                \
+    case 28: { constexpr int NP = 28; return CALL; }                \
+    default: { constexpr int NP = 32; return CALL; }                \
+  }
+
+// The forward's environment switches, read once per process (A/B timing and tuning):
+//   TSG_K1_FWD=v..   fwd_valu  the VALU kernel for every shape, also where a matrix-pipe forward applies (f32s and bf16 storage)
+//   TSG_K1_FWD=m..   fwd_mm    f32s only: scdm_fwd_mm_kernel (time-shared roles) in place of the role-specialised scdm_fwd_ws_kernel
+//   TSG_K1_TT=<rows> tt        rows per workgroup, when a multiple of 8 (matrix-pipe kernels: and at most kK1PRows)
+//   TSG_K1_PW=4      pw        scdm_fwd_ws_kernel with 4 + 4 waves where 8 + 8 would run
+// (TSG_K1_BWD is not here: tsg_scdm_bwd_mode changes it at run time, see g_bwd_mode.)
+struct K1Env { bool fwd_valu, fwd_mm; int tt, pw; };
+const K1Env& k1_env() {
+  static const K1Env env = [] {
+    const char* f = getenv("TSG_K1_FWD");
+    const char* t = getenv("TSG_K1_TT");
+    const char* p = getenv("TSG_K1_PW");
+    return K1Env{f && f[0] == 'v', f && f[0] == 'm', t ? atoi(t) : 0, p ? atoi(p) : 0};
+  }();
+  return env;
+}
+
+template <int NP> constexpr int max_ds() { return NP <= 20 ? 2048 : 1024; }        // sentence features a lane's registers hold
+
+// rows per workgroup: as many as still give every CU a workgroup (the Es prologue, the launch ramp and the store tail are paid
+// once per workgroup: 64 rows at 128 pairs x 128 clips measured 80 us vs 88 us for 32-row groups); TSG_K1_TT overrides
+int rows_per_workgroup(int B, int T, int floor, int cap) {
   int TT = 64;
-  while (TT > SUB && (long)B * cdiv(T, TT) < 256) TT >>= 1;
-  static const int tt_env = [] { const char* e = getenv("TSG_K1_TT"); return e ? atoi(e) : 0; }();   // tuning override
-  if (tt_env >= SUB && tt_env % SUB == 0) TT = tt_env;
-  const int tiles = cdiv(T, TT);
-  const size_t lds = sizeof(float) * ((size_t)(NP + 1) * roundup256(H) + (size_t)2 * SUB * NP);
-  if (H > 1024 || Ds > (NP <= 20 ? 2048 : 1024))
-    return set_error(TSG_E_SHAPE, "scdm_attn_fwd: H=%d (max 1024) / Ds=%d (max %d at N=%d) not supported",
-                     H, Ds, NP <= 20 ? 2048 : 1024, N);
-  if (lds > (size_t)kLdsBytes)
-    return set_error(TSG_E_LDS, "scdm_attn_fwd: N=%d H=%d needs %zu B of LDS (> %d)", N, H, lds, kLdsBytes);
-  auto kern = scdm_fwd_kernel<NP, R, GATE, ST>;
-  hipError_t e = allow_lds(kern, lds);
-  if (e != hipSuccess) return set_error((int)e, "scdm_attn_fwd: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-  launch_timed(kern, dim3(B * tiles), dim3(kFwdThreads), lds, st, a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, ablate_mask());
+  while (TT > floor && (long)B * cdiv(T, TT) < 256) TT >>= 1;
+  const int tt = k1_env().tt;
+  if (tt >= floor && tt % floor == 0 && tt <= cap) TT = tt;
+  return TT;
+}
+
+// scdm_fwd_ws_kernel as 8 producer + 8 consumer waves (two score waves per SIMD) while the consumer's VW strip fits 128 VGPRs
+// (8 < N <= 24; NP = 8 at 1024 threads spills; bf16 storage has no VW lo plane and 8-byte row pieces: 28 slots -- N = 25 --
+// still fit), else 4 + 4.  N = 25, 26 in fp32 storage run 8 + 8 with the words beyond 24 on the VALU (the XW = 1, 2 forms).
+template <int NP, typename ST> constexpr bool can_pw8() { return NP > 8 && (NP <= 24 || (storage_is_bf16<ST>::value && NP <= 28)); }
+
+// Which forward kernel a shape gets, and its launch geometry.  WS / MM: phase 2 on the bf16 matrix pipe, for dtype TSG_F32S
+// (split precision) and TSG_BF16 where the tiling applies (H = Ds = 256, 512, 1024 and the P tile fits the LDS); everything
+// else -- dtype TSG_F32 included -- plans the VALU kernel, whose own limits launch_fwd reports.
+struct FwdPlan { enum Kind { VALU, MM, WS } kind; int TT, tiles, threads; size_t lds; };
+template <int NP, typename ST>
+FwdPlan plan_fwd(int dtype, int B, int T, int N, int H, int Ds) {
+  const K1Env& env = k1_env();
+  const size_t es = (size_t)(NP + 1) * roundup256(H);
+  const size_t mm_lds = sizeof(float) * (es + (size_t)kK1PRows * 36 + 16 + 8 * kK1TrWave);
+  if (dtype != TSG_F32 && !env.fwd_valu && H == Ds && (Ds == 256 || Ds == 512 || Ds == 1024) && mm_lds <= (size_t)kLdsBytes) {
+    const int TT = rows_per_workgroup(B, T, 8, kK1PRows);
+    if (dtype == TSG_F32S && env.fwd_mm) return FwdPlan{FwdPlan::MM, TT, cdiv(T, TT), kFwdThreads, mm_lds};
+    const bool pw8 = env.pw != 4 && (can_pw8<NP, ST>() || (!storage_is_bf16<ST>::value && (N == 25 || N == 26)));
+    return FwdPlan{FwdPlan::WS, TT, cdiv(T, TT), pw8 ? 1024 : 512, mm_lds};
+  }
+  const int TT = rows_per_workgroup(B, T, kFwdWaves, INT_MAX);       // (one clip row per wave and sub-tile)
+  return FwdPlan{FwdPlan::VALU, TT, cdiv(T, TT), kFwdThreads, sizeof(float) * (es + (size_t)2 * kFwdWaves * NP)};
+}
+
+template <typename ST>
+using FwdKernel = void (*)(const ST*, const ST*, const float*, const ST*, ST*, float*, const ST*, const float*, int, int, int, int, int, int, int, int);
+
+template <int NP, bool GATE, typename ST, int PW, int XW = 0>
+FwdKernel<ST> pick_ct(int Ds) {                             // the Ds tiling of scdm_fwd_ws_kernel
+  return Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, PW, ST, XW> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, PW, ST, XW>
+                                                                              : scdm_fwd_ws_kernel<NP, GATE, 1, PW, ST, XW>;
+}
+
+template <int NP, bool GATE, typename ST>
+FwdKernel<ST> fwd_kernel_of(const FwdPlan& pl, int N, int Ds) {
+  if (pl.kind == FwdPlan::VALU) return scdm_fwd_kernel<NP, 1, GATE, ST>;
+  if constexpr (!storage_is_bf16<ST>::value) {
+    if (pl.kind == FwdPlan::MM)
+      return Ds == 1024 ? scdm_fwd_mm_kernel<NP, GATE, 4> : Ds == 512 ? scdm_fwd_mm_kernel<NP, GATE, 2> : scdm_fwd_mm_kernel<NP, GATE, 1>;
+  }
+  if (pl.threads == 1024) {
+    if constexpr (can_pw8<NP, ST>()) return pick_ct<NP, GATE, ST, 8>(Ds);
+    else if constexpr (NP == 28) return N == 25 ? pick_ct<NP, GATE, ST, 8, 1>(Ds) : pick_ct<NP, GATE, ST, 8, 2>(Ds);
+  }
+  return pick_ct<NP, GATE, ST, 4>(Ds);
+}
+
+template <int NP, bool GATE, typename ST>
+int launch_fwd(const void* a, const void* s, const void* w, const void* V, void* C, void* P, const void* gr, const void* gbias,
+               int B, int T, int N, int H, int Ds, int dtype, hipStream_t st) {
+  const FwdPlan pl = plan_fwd<NP, ST>(dtype, B, T, N, H, Ds);
+  if (H > 1024 || Ds > max_ds<NP>())
+    return set_error(TSG_E_SHAPE, "scdm_attn_fwd: H=%d (max 1024) / Ds=%d (max %d at N=%d) not supported", H, Ds, max_ds<NP>(), N);
+  if (pl.lds > (size_t)kLdsBytes)
+    return set_error(TSG_E_LDS, "scdm_attn_fwd: N=%d H=%d needs %zu B of LDS (> %d)", N, H, pl.lds, kLdsBytes);
+  const FwdKernel<ST> kern = fwd_kernel_of<NP, GATE, ST>(pl, N, Ds);
+  hipError_t e = allow_lds(kern, pl.lds);
+  if (e != hipSuccess) return set_error((int)e, "scdm_attn_fwd: hipFuncSetAttribute(%zu): %s", pl.lds, hipGetErrorString(e));
+  auto launch = [&](auto... args) {                                   // (the A/B kernel is not one tsg_time_next_launch brackets)
+    if (pl.kind == FwdPlan::MM) hipLaunchKernelGGL(kern, dim3(B * pl.tiles), dim3(pl.threads), pl.lds, st, args...);
+    else launch_timed(kern, dim3(B * pl.tiles), dim3(pl.threads), pl.lds, st, args...);
+  };
+  launch((const ST*)a, (const ST*)s, (const float*)w, (const ST*)V, (ST*)C, (float*)P, (const ST*)gr, (const float*)gbias,
+         B, T, N, H, Ds, pl.TT, pl.tiles, ablate_mask());
   return check_launch("scdm_attn_fwd");
 }
 
-template <int NP, bool GATE, typename ST>
-int launch_fwd_ws(const ST* a, const ST* s, const float* w, const ST* V, ST* C, float* P, const ST* gr, const float* gbias,
-                  int B, int T, int N, int H, int Ds, int TT, int tiles, size_t lds, hipStream_t st);
-
-// dtype TSG_F32S, fp32 storage: the forward with phase 2 on the bf16 matrix pipe where its tiling applies (Ds = 256, 512, 1024);
-// TSG_K1_FWD=valu in the environment keeps the VALU kernel (A/B timing).  Returns -1000 when the shape is not covered.
-template <int NP, bool GATE>
-int launch_fwd_mm(const float* a, const float* s, const float* w, const float* V, float* C, float* P,
-                  const float* gr, const float* gbias, int B, int T, int N, int H, int Ds, hipStream_t st) {
-  static const bool valu_only = [] { const char* e = getenv("TSG_K1_FWD"); return e && e[0] == 'v'; }();
-  if (valu_only || H != Ds || (Ds != 256 && Ds != 512 && Ds != 1024)) return -1000;
-  int TT = 64;                               // rows per workgroup: as many as still give every CU a workgroup (as launch_fwd)
-  while (TT > 8 && (long)B * cdiv(T, TT) < 256) TT >>= 1;
-  static const int tt_env = [] { const char* e = getenv("TSG_K1_TT"); return e ? atoi(e) : 0; }();
-  if (tt_env >= 8 && tt_env % 8 == 0 && tt_env <= kK1PRows) TT = tt_env;
-  const int tiles = cdiv(T, TT);
-  const size_t lds = sizeof(float) * ((size_t)(NP + 1) * roundup256(H) + (size_t)kK1PRows * 36 + 16 + 8 * kK1TrWave);
-  if (lds > (size_t)kLdsBytes) return -1000;
-  static const bool mm_only = [] { const char* e = getenv("TSG_K1_FWD"); return e && e[0] == 'm'; }();   // A/B: time-shared roles
-  if (mm_only) {
-    auto kern = Ds == 1024 ? scdm_fwd_mm_kernel<NP, GATE, 4> : Ds == 512 ? scdm_fwd_mm_kernel<NP, GATE, 2> : scdm_fwd_mm_kernel<NP, GATE, 1>;
-    hipError_t e = allow_lds(kern, lds);
-    if (e != hipSuccess) return set_error((int)e, "scdm_attn_fwd: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(B * tiles), dim3(kFwdThreads), lds, st, a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, ablate_mask());
-    return check_launch("scdm_attn_fwd");
-  }
-  return launch_fwd_ws<NP, GATE, float>(a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, lds, st);
-}
-
-// role-specialised waves: 8 producers + 8 consumers (two score waves per SIMD) while the consumer's VW strip fits 128 VGPRs
-// (8 < N <= 24), else 4 + 4.  TSG_K1_PW=4 forces the latter (A/B timing).  ST = float (TSG_F32S) or bf16_t (TSG_BF16).
-template <int NP, bool GATE, typename ST>
-int launch_fwd_ws(const ST* a, const ST* s, const float* w, const ST* V, ST* C, float* P, const ST* gr, const float* gbias,
-                  int B, int T, int N, int H, int Ds, int TT, int tiles, size_t lds, hipStream_t st) {
-  static const int pw_env = [] { const char* e = getenv("TSG_K1_PW"); return e ? atoi(e) : 0; }();
-  // (NP = 8 at 1024 threads spills: 4 + 4 there; bf16 storage has no VW lo plane and 8-byte row pieces: 28 slots -- N = 25 -- still fit)
-  constexpr bool kCanPw8 = NP > 8 && (NP <= 24 || (storage_is_bf16<ST>::value && NP <= 28));
-  const bool pw8 = kCanPw8 && pw_env != 4;
-  void (*kern)(const ST*, const ST*, const float*, const ST*, ST*, float*, const ST*, const float*, int, int, int, int, int, int, int, int);
-  if constexpr (NP == 28 && !storage_is_bf16<ST>::value) {
-    // N = 25, 26 in fp32 storage: 8 + 8 waves with the words beyond 24 on the VALU (round-4 review item 3a); N = 27, 28: 4 + 4
-    if ((N == 25 || N == 26) && pw_env != 4) {
-      if (N == 25) kern = Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, 8, ST, 1> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, 8, ST, 1> : scdm_fwd_ws_kernel<NP, GATE, 1, 8, ST, 1>;
-      else kern = Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, 8, ST, 2> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, 8, ST, 2> : scdm_fwd_ws_kernel<NP, GATE, 1, 8, ST, 2>;
-      hipError_t e = allow_lds(kern, lds);
-      if (e != hipSuccess) return set_error((int)e, "scdm_attn_fwd: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-      launch_timed(kern, dim3(B * tiles), dim3(1024), lds, st, a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, ablate_mask());
-      return check_launch("scdm_attn_fwd");
-    }
-  }
-  if constexpr (kCanPw8) {
-    if (pw8) kern = Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, 8, ST> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, 8, ST> : scdm_fwd_ws_kernel<NP, GATE, 1, 8, ST>;
-    else kern = Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, 4, ST> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, 4, ST> : scdm_fwd_ws_kernel<NP, GATE, 1, 4, ST>;
-  } else {
-    kern = Ds == 1024 ? scdm_fwd_ws_kernel<NP, GATE, 4, 4, ST> : Ds == 512 ? scdm_fwd_ws_kernel<NP, GATE, 2, 4, ST> : scdm_fwd_ws_kernel<NP, GATE, 1, 4, ST>;
-  }
-  hipError_t e = allow_lds(kern, lds);
-  if (e != hipSuccess) return set_error((int)e, "scdm_attn_fwd: hipFuncSetAttribute(%zu): %s", lds, hipGetErrorString(e));
-  launch_timed(kern, dim3(B * tiles), dim3(pw8 ? 1024 : 512), lds, st, a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, ablate_mask());
-  return check_launch("scdm_attn_fwd");
-}
-
-// dtype TSG_BF16: the same kernel on bf16 storage where its tiling applies (H = Ds = 256, 512, 1024); -1000 otherwise (the VALU kernel runs).
-// TSG_K1_FWD=valu keeps the VALU kernel (A/B timing).
-template <int NP, bool GATE>
-int launch_fwd_ws_bf16(const bf16_t* a, const bf16_t* s, const float* w, const bf16_t* V, bf16_t* C, float* P,
-                       const bf16_t* gr, const float* gbias, int B, int T, int N, int H, int Ds, hipStream_t st) {
-  static const bool valu_only = [] { const char* e = getenv("TSG_K1_FWD"); return e && e[0] == 'v'; }();
-  if (valu_only || H != Ds || (Ds != 256 && Ds != 512 && Ds != 1024)) return -1000;
-  int TT = 64;
-  while (TT > 8 && (long)B * cdiv(T, TT) < 256) TT >>= 1;
-  static const int tt_env = [] { const char* e = getenv("TSG_K1_TT"); return e ? atoi(e) : 0; }();
-  if (tt_env >= 8 && tt_env % 8 == 0 && tt_env <= kK1PRows) TT = tt_env;
-  const int tiles = cdiv(T, TT);
-  const size_t lds = sizeof(float) * ((size_t)(NP + 1) * roundup256(H) + (size_t)kK1PRows * 36 + 16 + 8 * kK1TrWave);
-  if (lds > (size_t)kLdsBytes) return -1000;
-  return launch_fwd_ws<NP, GATE, bf16_t>(a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, TT, tiles, lds, st);
+template <bool GATE>
+int scdm_fwd_entry(const void* a, const void* s, const void* w, const void* V, void* C, void* P, const void* gr, const void* gbias,
+                   int B, int T, int N, int H, int Ds, int dtype, void* stream) {
+  auto st = static_cast<hipStream_t>(stream);
+  if (dtype == TSG_BF16) TSG_DISPATCH_NP(roundup(N, 4), (launch_fwd<NP, GATE, bf16_t>(a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, dtype, st)));
+  TSG_DISPATCH_NP(roundup(N, 4), (launch_fwd<NP, GATE, float>(a, s, w, V, C, P, gr, gbias, B, T, N, H, Ds, dtype, st)));
 }
 
 // Two-kernel path (kept for shapes whose P / de tiles do not fit the fused kernel's LDS, and for A/B timing with
@@ -2212,8 +2225,6 @@ int launch_bwd_split(const float* a, const float* s, const float* w, const float
                const float* dC, float* da, float* ds, float* dw, float* dV, float* de,
                const float* gr, const float* gbias, float* dbias, float* dr, float* dG_ws,
                int B, int T, int N, int H, int Ds, hipStream_t st) {
-  if (Ds > (NP <= 20 ? 2048 : 1024))
-    return set_error(TSG_E_SHAPE, "scdm_attn_bwd: Ds=%d (max %d at N=%d) not supported", Ds, NP <= 20 ? 2048 : 1024, N);
   hipLaunchKernelGGL(zero3_kernel, dim3(4), dim3(256), 0, st, (unsigned*)dw, H, (unsigned*)dbias, GATE ? Ds : 0, (unsigned*)nullptr, 0);
   const int tiles = cdiv(T, 32);
   hipLaunchKernelGGL((scdm_bwd_rows_kernel<NP, GATE>), dim3(B * tiles), dim3(kFwdThreads), 0, st, V, P, dC, de, gr, gbias,
@@ -2242,7 +2253,6 @@ static int bwd_mode() {
   }
   return v;
 }
-static bool want_split() { return bwd_mode() == 1; }
 
 // The plan launch_bwd runs for a shape: which fused variant, and whether the one-launch kernel takes it at all.
 struct BwdChoice { FusedPlan plan; bool mrow; bool fused; };
@@ -2260,34 +2270,36 @@ BwdChoice choose_bwd(int B, int T, int N, int H, int Ds) {
   // are all dispatched as long as that window fits the workgroups the chip holds at once (one per CU).  Half the CUs is the
   // margin kept for CUs a collective or another stream occupies; beyond it the two-kernel path (no waiting) runs.
   const bool window_ok = pl.parts == 1 || 8 * (pl.parts - 1) + 1 <= device_cu_count() / 2;
-  const bool ds_ok = Ds <= (NP <= 20 ? 2048 : 1024);
-  return BwdChoice{pl, mrow, ds_ok && pl.ok && window_ok && !want_split()};
+  return BwdChoice{pl, mrow, Ds <= max_ds<NP>() && pl.ok && window_ok && bwd_mode() != 1};
 }
 
 inline long long split_ws_bytes(int B, int T, int N, int Ds, bool gate) {
   return (long long)sizeof(float) * ((long long)B * T * roundup(N, 4) + (gate ? (long long)B * T * Ds : 0));
 }
+template <int NP>
+long long bwd_ws_bytes(int B, int T, int N, int H, int Ds, bool gate) {      // either path (and either fused variant) can run in it
+  return std::max({fused_plan<NP, true>(B, T, N, H, Ds).ws_bytes, fused_plan<NP, false>(B, T, N, H, Ds).ws_bytes, split_ws_bytes(B, T, N, Ds, gate)});
+}
 
 template <int NP, bool GATE, typename ST>
-int launch_bwd(const ST* a, const ST* s, const float* w, const ST* V, const float* P,
-               const ST* dC, ST* da, ST* ds, float* dw, ST* dV, const ST* gr, const float* gbias,
-               float* dbias, ST* dr, void* ws, long long ws_bytes, int B, int T, int N, int H, int Ds, hipStream_t st) {
+int launch_bwd(const void* a, const void* s, const void* w, const void* V, const void* gbias, const void* gr, const void* P,
+               const void* dC, void* da, void* ds, void* dw, void* dV, void* dbias, void* dr, void* ws, long long ws_bytes,
+               int B, int T, int N, int H, int Ds, hipStream_t st) {
   const char* fn = GATE ? "tsg_scdm_gate_bwd" : "tsg_scdm_attn_bwd";
-  if (Ds > (NP <= 20 ? 2048 : 1024))
-    return set_error(TSG_E_SHAPE, "%s: Ds=%d (max %d at N=%d) not supported", fn, Ds, NP <= 20 ? 2048 : 1024, N);
+  if (Ds > max_ds<NP>()) return set_error(TSG_E_SHAPE, "%s: Ds=%d (max %d at N=%d) not supported", fn, Ds, max_ds<NP>(), N);
   const BwdChoice ch = choose_bwd<NP>(B, T, N, H, Ds);
   const FusedPlan& pl = ch.plan;
-  const bool mrow = ch.mrow;
   if (ch.fused) {
     if (ws_bytes < pl.ws_bytes) return set_error(TSG_E_SHAPE, "%s: workspace of %lld B < %lld B (tsg_scdm_bwd_ws_bytes)", fn, ws_bytes, pl.ws_bytes);
     float* xch = static_cast<float*>(ws);
     unsigned* cnt = reinterpret_cast<unsigned*>(xch + (size_t)B * pl.parts * T * NP);
     hipLaunchKernelGGL(zero3_kernel, dim3(4), dim3(256), 0, st, (unsigned*)dw, H, (unsigned*)dbias, GATE ? Ds : 0, cnt, B);
-    auto kern = mrow ? scdm_bwd_fused_kernel<NP, GATE, true, ST> : scdm_bwd_fused_kernel<NP, GATE, false, ST>;
+    auto kern = ch.mrow ? scdm_bwd_fused_kernel<NP, GATE, true, ST> : scdm_bwd_fused_kernel<NP, GATE, false, ST>;
     hipError_t e = allow_lds(kern, pl.lds);
     if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute(%zu): %s", fn, pl.lds, hipGetErrorString(e));
-    launch_timed(kern, dim3(pl.grid), dim3(kFusedThreads), pl.lds, st, a, s, w, V, P, dC, gr, gbias, da, ds, dw, dV, dbias, dr,
-                       xch, cnt, error_sink(), B, T, N, H, Ds, pl.parts, pl.SP, ablate_mask());
+    launch_timed(kern, dim3(pl.grid), dim3(kFusedThreads), pl.lds, st, (const ST*)a, (const ST*)s, (const float*)w, (const ST*)V,
+                 (const float*)P, (const ST*)dC, (const ST*)gr, (const float*)gbias, (ST*)da, (ST*)ds, (float*)dw, (ST*)dV, (float*)dbias,
+                 (ST*)dr, xch, cnt, error_sink(), B, T, N, H, Ds, pl.parts, pl.SP, ablate_mask());
     return check_launch(fn);
   }
   if constexpr (storage_is_bf16<ST>::value) {
@@ -2298,26 +2310,21 @@ int launch_bwd(const ST* a, const ST* s, const float* w, const ST* V, const floa
     if (ws_bytes < split_ws_bytes(B, T, N, Ds, GATE))
       return set_error(TSG_E_SHAPE, "%s: workspace of %lld B < %lld B (tsg_scdm_bwd_ws_bytes)", fn, ws_bytes, split_ws_bytes(B, T, N, Ds, GATE));
     float* de = static_cast<float*>(ws);
-    float* dG = de + (size_t)B * T * roundup(N, 4);
-    return launch_bwd_split<NP, GATE>(a, s, w, V, P, dC, da, ds, dw, dV, de, gr, gbias, dbias, dr, GATE ? dG : nullptr, B, T, N, H, Ds, st);
+    float* dG = GATE ? de + (size_t)B * T * roundup(N, 4) : nullptr;
+    return launch_bwd_split<NP, GATE>((const float*)a, (const float*)s, (const float*)w, (const float*)V, (const float*)P, (const float*)dC,
+                                      (float*)da, (float*)ds, (float*)dw, (float*)dV, de, (const float*)gr, (const float*)gbias,
+                                      (float*)dbias, (float*)dr, dG, B, T, N, H, Ds, st);
   }
 }
 
-int check_common(const char* fn, std::initializer_list<const void*> ptrs, int B, int T, int N, int H, int Ds, int dtype) {
-  for (const void* p : ptrs) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  if (dtype != TSG_F32 && dtype != TSG_BF16 && dtype != TSG_F32S)
-    return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S, or TSG_BF16 = bf16 storage of the activations)", fn, dtype);
-  if (B <= 0 || T <= 0 || N <= 0 || H <= 0 || Ds <= 0)
-    return set_error(TSG_E_SHAPE, "%s: non-positive dimension B=%d T=%d N=%d H=%d Ds=%d", fn, B, T, N, H, Ds);
-  if (N > 32) return set_error(TSG_E_SHAPE, "%s: N=%d > 32 words not supported", fn, N);
-  // the kernels keep B * tiles in an int grid and B * T rows in 32-bit row arithmetic (found by the host sanitizer build: the workspace plan of
-  // B = T = 2^30 overflowed a long long)
-  if ((long long)B * T >= (1LL << 31)) return set_error(TSG_E_SHAPE, "%s: B * T = %lld rows (limit 2^31 - 1)", fn, (long long)B * T);
-  if (H % 4 || Ds % 4) return set_error(TSG_E_ALIGN, "%s: H=%d and Ds=%d must be multiples of 4", fn, H, Ds);
-  return 0;
+template <bool GATE>
+int scdm_bwd_entry(const void* a, const void* s, const void* w, const void* V, const void* gbias, const void* gr, const void* P,
+                   const void* dC, void* da, void* ds, void* dw, void* dV, void* dbias, void* dr, void* ws, long long ws_bytes,
+                   int B, int T, int N, int H, int Ds, int dtype, void* stream) {
+  auto st = static_cast<hipStream_t>(stream);
+  if (dtype == TSG_BF16)
+    TSG_DISPATCH_NP(roundup(N, 4), (launch_bwd<NP, GATE, bf16_t>(a, s, w, V, gbias, gr, P, dC, da, ds, dw, dV, dbias, dr, ws, ws_bytes, B, T, N, H, Ds, st)));
+  TSG_DISPATCH_NP(roundup(N, 4), (launch_bwd<NP, GATE, float>(a, s, w, V, gbias, gr, P, dC, da, ds, dw, dV, dbias, dr, ws, ws_bytes, B, T, N, H, Ds, st)));
 }
 
 }  // namespace
@@ -2325,63 +2332,39 @@ int check_common(const char* fn, std::initializer_list<const void*> ptrs, int B,
 
 using namespace tsg;
 
-#define TSG_DISPATCH_NP(NPV, CALL)                                  \
-  switch (NPV) {                                                    \
-    case 4: { constexpr int NP = 4; return CALL; }                  \
-    case 8: { constexpr int NP = 8; return CALL; }                  \
-    case 12: { constexpr int NP = 12; return CALL; }                \
-    case 16: { constexpr int NP = 16; return CALL; }                \
-    case 20: { constexpr int NP = 20; return CALL; }                \
-    case 24: { constexpr int NP = 24; return CALL; }                \
-    case 28: { constexpr int NP = 28; return CALL; }                \
-    default: { constexpr int NP = 32; return CALL; }                \
-  }
-
 extern "C" int tsg_scdm_attn_fwd(const void* a, const void* s, const void* w, const void* sent, void* C,
                                  void* P, int B, int T, int N, int H, int Ds, int dtype, void* stream) {
-  int rc = check_common("tsg_scdm_attn_fwd", {a, s, w, sent, C, P}, B, T, N, H, Ds, dtype);
-  if (rc) return rc;
-  const int np = roundup(N, 4);
-  auto st = static_cast<hipStream_t>(stream);
-  if (dtype == TSG_BF16) {
-    using S = bf16_t;
-    auto ws = [&]() -> int {
-      TSG_DISPATCH_NP(np, (launch_fwd_ws_bf16<NP, false>((const S*)a, (const S*)s, (const float*)w, (const S*)sent,
-                                                         (S*)C, (float*)P, nullptr, nullptr, B, T, N, H, Ds, st)));
-    };
-    rc = ws();
-    if (rc != -1000) return rc;
-    TSG_DISPATCH_NP(np, (launch_fwd<NP, false, S>((const S*)a, (const S*)s, (const float*)w, (const S*)sent,
-                                                  (S*)C, (float*)P, nullptr, nullptr, B, T, N, H, Ds, st)));
-  }
-  if (dtype == TSG_F32S) {
-    auto mm = [&]() -> int {
-      TSG_DISPATCH_NP(np, (launch_fwd_mm<NP, false>((const float*)a, (const float*)s, (const float*)w, (const float*)sent,
-                                                    (float*)C, (float*)P, nullptr, nullptr, B, T, N, H, Ds, st)));
-    };
-    rc = mm();
-    if (rc != -1000) return rc;
-  }
-  TSG_DISPATCH_NP(np, (launch_fwd<NP, false, float>((const float*)a, (const float*)s, (const float*)w, (const float*)sent,
-                                                    (float*)C, (float*)P, nullptr, nullptr, B, T, N, H, Ds, st)));
+  if (int rc = check_scdm_args("tsg_scdm_attn_fwd", {a, s, w, sent, C, P}, B, T, N, 32, H, Ds, dtype)) return rc;
+  return scdm_fwd_entry<false>(a, s, w, sent, C, P, nullptr, nullptr, B, T, N, H, Ds, dtype, stream);
+}
+
+extern "C" int tsg_scdm_gate_fwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias,
+                                 const void* r, void* out, void* P, int B, int T, int N, int H, int Ds, int dtype,
+                                 void* stream) {
+  if (int rc = check_scdm_args("tsg_scdm_gate_fwd", {a, s, w, VW, gbias, r, out, P}, B, T, N, 32, H, Ds, dtype)) return rc;
+  return scdm_fwd_entry<true>(a, s, w, VW, out, P, r, gbias, B, T, N, H, Ds, dtype, stream);
+}
+
+extern "C" int tsg_scdm_attn_bwd(const void* a, const void* s, const void* w, const void* sent,
+                                 const void* P, const void* dC, void* da, void* ds, void* dw, void* dsent,
+                                 void* ws, long long ws_bytes, int B, int T, int N, int H, int Ds, int dtype, void* stream) {
+  if (int rc = check_scdm_args("tsg_scdm_attn_bwd", {a, s, w, sent, P, dC, da, ds, dw, dsent, ws}, B, T, N, 32, H, Ds, dtype)) return rc;
+  return scdm_bwd_entry<false>(a, s, w, sent, nullptr, nullptr, P, dC, da, ds, dw, dsent, nullptr, nullptr, ws, ws_bytes,
+                               B, T, N, H, Ds, dtype, stream);
+}
+
+extern "C" int tsg_scdm_gate_bwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias,
+                                 const void* r, const void* P, const void* dout, void* da, void* ds, void* dw,
+                                 void* dVW, void* dgbias, void* dr, void* ws, long long ws_bytes,
+                                 int B, int T, int N, int H, int Ds, int dtype, void* stream) {
+  if (int rc = check_scdm_args("tsg_scdm_gate_bwd", {a, s, w, VW, gbias, r, P, dout, da, ds, dw, dVW, dgbias, dr, ws},
+                               B, T, N, 32, H, Ds, dtype)) return rc;
+  return scdm_bwd_entry<true>(a, s, w, VW, gbias, r, P, dout, da, ds, dw, dVW, dgbias, dr, ws, ws_bytes, B, T, N, H, Ds, dtype, stream);
 }
 
 extern "C" long long tsg_scdm_bwd_ws_bytes(int B, int T, int N, int H, int Ds, int gate) {
   if (B <= 0 || T <= 0 || N <= 0 || N > 32 || H <= 0 || Ds <= 0 || (long long)B * T >= (1LL << 31)) return 0;     // (shapes the entry points reject)
-  const int np = roundup(N, 4);
-  const long long split = split_ws_bytes(B, T, N, Ds, gate != 0);
-  long long fused = 0;
-  switch (np) {
-    case 4: fused = std::max(fused_plan<4, true>(B, T, N, H, Ds).ws_bytes, fused_plan<4, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 8: fused = std::max(fused_plan<8, true>(B, T, N, H, Ds).ws_bytes, fused_plan<8, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 12: fused = std::max(fused_plan<12, true>(B, T, N, H, Ds).ws_bytes, fused_plan<12, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 16: fused = std::max(fused_plan<16, true>(B, T, N, H, Ds).ws_bytes, fused_plan<16, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 20: fused = std::max(fused_plan<20, true>(B, T, N, H, Ds).ws_bytes, fused_plan<20, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 24: fused = std::max(fused_plan<24, true>(B, T, N, H, Ds).ws_bytes, fused_plan<24, false>(B, T, N, H, Ds).ws_bytes); break;
-    case 28: fused = std::max(fused_plan<28, true>(B, T, N, H, Ds).ws_bytes, fused_plan<28, false>(B, T, N, H, Ds).ws_bytes); break;
-    default: fused = std::max(fused_plan<32, true>(B, T, N, H, Ds).ws_bytes, fused_plan<32, false>(B, T, N, H, Ds).ws_bytes); break;
-  }
-  return fused > split ? fused : split;       // either path can run in it
+  TSG_DISPATCH_NP(roundup(N, 4), (bwd_ws_bytes<NP>(B, T, N, H, Ds, gate != 0)));
 }
 
 extern "C" int tsg_scdm_bwd_mode(int mode) {
@@ -2392,80 +2375,7 @@ extern "C" int tsg_scdm_bwd_mode(int mode) {
 
 extern "C" int tsg_scdm_bwd_fused_ok(int B, int T, int N, int H, int Ds) {
   if (B <= 0 || T <= 0 || N <= 0 || N > 32 || H <= 0 || Ds <= 0 || H % 4 || Ds % 4) return 0;
-  const int np = roundup(N, 4);
-  TSG_DISPATCH_NP(np, (choose_bwd<NP>(B, T, N, H, Ds).fused ? 1 : 0));
-}
-
-extern "C" int tsg_scdm_attn_bwd(const void* a, const void* s, const void* w, const void* sent,
-                                 const void* P, const void* dC, void* da, void* ds, void* dw, void* dsent,
-                                 void* ws, long long ws_bytes, int B, int T, int N, int H, int Ds, int dtype, void* stream) {
-  int rc = check_common("tsg_scdm_attn_bwd", {a, s, w, sent, P, dC, da, ds, dw, dsent, ws}, B, T, N, H, Ds, dtype);
-  if (rc) return rc;
-  const int np = roundup(N, 4);
-  auto st = static_cast<hipStream_t>(stream);
-  if (dtype == TSG_BF16) {
-    using S = bf16_t;
-    TSG_DISPATCH_NP(np, (launch_bwd<NP, false, S>((const S*)a, (const S*)s, (const float*)w, (const S*)sent,
-                                                  (const float*)P, (const S*)dC, (S*)da, (S*)ds, (float*)dw,
-                                                  (S*)dsent, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes,
-                                                  B, T, N, H, Ds, st)));
-  }
-  TSG_DISPATCH_NP(np, (launch_bwd<NP, false, float>((const float*)a, (const float*)s, (const float*)w, (const float*)sent,
-                                                    (const float*)P, (const float*)dC, (float*)da, (float*)ds, (float*)dw,
-                                                    (float*)dsent, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes,
-                                                    B, T, N, H, Ds, st)));
-}
-
-extern "C" int tsg_scdm_gate_fwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias,
-                                 const void* r, void* out, void* P, int B, int T, int N, int H, int Ds, int dtype,
-                                 void* stream) {
-  int rc = check_common("tsg_scdm_gate_fwd", {a, s, w, VW, gbias, r, out, P}, B, T, N, H, Ds, dtype);
-  if (rc) return rc;
-  const int np = roundup(N, 4);
-  auto st = static_cast<hipStream_t>(stream);
-  if (dtype == TSG_BF16) {
-    using S = bf16_t;
-    auto ws = [&]() -> int {
-      TSG_DISPATCH_NP(np, (launch_fwd_ws_bf16<NP, true>((const S*)a, (const S*)s, (const float*)w, (const S*)VW,
-                                                        (S*)out, (float*)P, (const S*)r, (const float*)gbias, B, T, N, H, Ds, st)));
-    };
-    rc = ws();
-    if (rc != -1000) return rc;
-    TSG_DISPATCH_NP(np, (launch_fwd<NP, true, S>((const S*)a, (const S*)s, (const float*)w, (const S*)VW,
-                                                 (S*)out, (float*)P, (const S*)r, (const float*)gbias, B, T, N, H, Ds, st)));
-  }
-  if (dtype == TSG_F32S) {
-    auto mm = [&]() -> int {
-      TSG_DISPATCH_NP(np, (launch_fwd_mm<NP, true>((const float*)a, (const float*)s, (const float*)w, (const float*)VW,
-                                                   (float*)out, (float*)P, (const float*)r, (const float*)gbias, B, T, N, H, Ds, st)));
-    };
-    rc = mm();
-    if (rc != -1000) return rc;
-  }
-  TSG_DISPATCH_NP(np, (launch_fwd<NP, true, float>((const float*)a, (const float*)s, (const float*)w, (const float*)VW,
-                                                   (float*)out, (float*)P, (const float*)r, (const float*)gbias, B, T, N, H, Ds, st)));
-}
-
-extern "C" int tsg_scdm_gate_bwd(const void* a, const void* s, const void* w, const void* VW, const void* gbias,
-                                 const void* r, const void* P, const void* dout, void* da, void* ds, void* dw,
-                                 void* dVW, void* dgbias, void* dr, void* ws, long long ws_bytes,
-                                 int B, int T, int N, int H, int Ds, int dtype, void* stream) {
-  int rc = check_common("tsg_scdm_gate_bwd", {a, s, w, VW, gbias, r, P, dout, da, ds, dw, dVW, dgbias, dr, ws},
-                        B, T, N, H, Ds, dtype);
-  if (rc) return rc;
-  const int np = roundup(N, 4);
-  auto st = static_cast<hipStream_t>(stream);
-  if (dtype == TSG_BF16) {
-    using S = bf16_t;
-    TSG_DISPATCH_NP(np, (launch_bwd<NP, true, S>((const S*)a, (const S*)s, (const float*)w, (const S*)VW,
-                                                 (const float*)P, (const S*)dout, (S*)da, (S*)ds, (float*)dw,
-                                                 (S*)dVW, (const S*)r, (const float*)gbias,
-                                                 (float*)dgbias, (S*)dr, ws, ws_bytes, B, T, N, H, Ds, st)));
-  }
-  TSG_DISPATCH_NP(np, (launch_bwd<NP, true, float>((const float*)a, (const float*)s, (const float*)w, (const float*)VW,
-                                                   (const float*)P, (const float*)dout, (float*)da, (float*)ds, (float*)dw,
-                                                   (float*)dVW, (const float*)r, (const float*)gbias,
-                                                   (float*)dgbias, (float*)dr, ws, ws_bytes, B, T, N, H, Ds, st)));
+  TSG_DISPATCH_NP(roundup(N, 4), (choose_bwd<NP>(B, T, N, H, Ds).fused ? 1 : 0));
 }
 
 #ifdef TSG_K1_TICKS

@@ -753,17 +753,7 @@ __global__ __launch_bounds__(kColThreads) void scdm_long_bwd_dv_kernel(
 // host
 // ------------------------------------------------------------------------------------------
 int check_long(const char* fn, std::initializer_list<const void*> ptrs, int B, int T, int N, int H, int Ds, int dtype) {
-  for (const void* p : ptrs) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  if (dtype != TSG_F32 && dtype != TSG_BF16 && dtype != TSG_F32S)
-    return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S, or TSG_BF16 = bf16 storage of the activations)", fn, dtype);
-  if (B <= 0 || T <= 0 || N <= 0 || H <= 0 || Ds <= 0)
-    return set_error(TSG_E_SHAPE, "%s: non-positive dimension B=%d T=%d N=%d H=%d Ds=%d", fn, B, T, N, H, Ds);
-  if (N > kLongMaxWords) return set_error(TSG_E_SHAPE, "%s: N=%d > %d words not supported", fn, N, kLongMaxWords);
-  if ((long long)B * T >= (1LL << 31)) return set_error(TSG_E_SHAPE, "%s: B * T = %lld rows (limit 2^31 - 1)", fn, (long long)B * T);
-  if (H % 4 || Ds % 4) return set_error(TSG_E_ALIGN, "%s: H=%d and Ds=%d must be multiples of 4", fn, H, Ds);
+  if (int rc = check_scdm_args(fn, ptrs, B, T, N, kLongMaxWords, H, Ds, dtype)) return rc;
   if (H > kLongMaxH) return set_error(TSG_E_SHAPE, "%s: H=%d > %d not supported", fn, H, kLongMaxH);
   if (Ds > kLongMaxDs) return set_error(TSG_E_SHAPE, "%s: Ds=%d > %d not supported", fn, Ds, kLongMaxDs);
   return 0;

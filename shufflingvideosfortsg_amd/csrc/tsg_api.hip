@@ -72,6 +72,23 @@ int set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+int check_scdm_args(const char* fn, std::initializer_list<const void*> ptrs, int B, int T, int N, int max_words, int H, int Ds, int dtype) {
+  for (const void* p : ptrs) {
+    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
+    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
+  }
+  if (dtype != TSG_F32 && dtype != TSG_BF16 && dtype != TSG_F32S)
+    return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S, or TSG_BF16 = bf16 storage of the activations)", fn, dtype);
+  if (B <= 0 || T <= 0 || N <= 0 || H <= 0 || Ds <= 0)
+    return set_error(TSG_E_SHAPE, "%s: non-positive dimension B=%d T=%d N=%d H=%d Ds=%d", fn, B, T, N, H, Ds);
+  if (N > max_words) return set_error(TSG_E_SHAPE, "%s: N=%d > %d words not supported", fn, N, max_words);
+  // the kernels keep B * tiles in an int grid and B * T rows in 32-bit row arithmetic (found by the host sanitizer build: the workspace plan of
+  // B = T = 2^30 overflowed a long long)
+  if ((long long)B * T >= (1LL << 31)) return set_error(TSG_E_SHAPE, "%s: B * T = %lld rows (limit 2^31 - 1)", fn, (long long)B * T);
+  if (H % 4 || Ds % 4) return set_error(TSG_E_ALIGN, "%s: H=%d and Ds=%d must be multiples of 4", fn, H, Ds);
+  return 0;
+}
+
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) return 0;

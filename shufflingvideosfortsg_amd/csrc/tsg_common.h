@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../include/tsg_hip.h"
 
@@ -18,6 +19,10 @@ constexpr float kLog2e = 1.4426950408889634f;
 // ---- host side ---------------------------------------------------------------------------
 int set_error(int code, const char* fmt, ...);   // stores a thread-local message, returns code
 int check_launch(const char* what);              // hipGetLastError() -> 0 or positive hipError_t
+// The argument check every SCDM entry point (scdm_attn.hip: up to 32 words, scdm_long.hip: up to 128) starts with: pointers non-NULL
+// and 16-byte aligned, a known dtype, positive dimensions, N <= max_words, B * T < 2^31, H and Ds multiples of 4 -- in this order,
+// the first failure reported through set_error under the entry point's name `fn`.
+int check_scdm_args(const char* fn, std::initializer_list<const void*> ptrs, int B, int T, int N, int max_words, int H, int Ds, int dtype);
 // Where a kernel with a bounded wait reports an expiry: `host` = the registered sink (tsg_error_sink: host-mapped memory the
 // host polls without synchronising), `dev` = the registered device word (tsg_error_word: device memory the optimizer's
 // skip-the-update guard reads on the device, so a corrupted backward never reaches the parameters -- also under graph replay,

@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import ctypes
 import os
+from dataclasses import dataclass
+
 import torch
 
 from . import _lib
@@ -607,25 +609,110 @@ def scdm_bwd_fused_ok(B: int, T: int, N: int, H: int, Ds: int) -> bool:
     return bool(load().tsg_scdm_bwd_fused_ok(B, T, N, H, Ds))
 
 
+@dataclass(frozen=True)
+class _ScdmFamily:
+    """One kernel family behind K1 / K1g: what the two autograd nodes below need to know about it.  (Not a tuple: autocast's ``custom_fwd`` rebuilds
+    every tuple among a node's arguments.)"""
+    attn: str                 # the public functions' names (error texts)
+    gate: str
+    fwd: str                  # the four entry points (include/tsg_hip.h)
+    gate_fwd: str
+    bwd: str
+    gate_bwd: str
+    ws_bytes: str             # the backward's workspace-size function
+    exchange: bool            # the backward exchanges partials between workgroups: it wants ``_gate_before()`` (co-resident workgroup pairs), and a bf16
+                              # shape that ``scdm_bwd_fused_ok`` rejects runs through fp32 copies (the two-kernel path is fp32-storage only)
+    word_limit: bool          # N is checked here against ``scdm_long_max_words()`` (K1 leaves its 32 words to the library)
+
+
+_K1 = _ScdmFamily("scdm_attn", "scdm_gate", "tsg_scdm_attn_fwd", "tsg_scdm_gate_fwd", "tsg_scdm_attn_bwd", "tsg_scdm_gate_bwd",
+                  "tsg_scdm_bwd_ws_bytes", exchange=True, word_limit=False)
+# up to 128 words (tsg_scdm_long_*): the bf16 kernels take every shape the fp32 ones take, and the backward's five launches exchange nothing
+_K1L = _ScdmFamily("scdm_attn_long", "scdm_gate_long", "tsg_scdm_long_fwd", "tsg_scdm_long_gate_fwd", "tsg_scdm_long_bwd", "tsg_scdm_long_gate_bwd",
+                   "tsg_scdm_long_ws_bytes", exchange=False, word_limit=True)
+
+
+def _scdm_operands(fam, a, s, w, V, gbias=None, r=None):
+    """The operands as the kernels take them -- bf16 storage (a, s, V, r and the output as bf16) when the clip-side activation is bf16, w / gbias
+    fp32 always -- and (B, T, N, H, Ds) after the shape check.  ``r`` given: the gate-fused form."""
+    gate = r is not None
+    what = fam.gate if gate else fam.attn
+    bf = (r if gate else a).dtype == _BF
+    a, s, w, V = _act(a, bf), _act(s, bf), _f32p(w), _act(V, bf)
+    if gate:
+        gbias, r = _f32p(gbias), _act(r, bf)
+    B, T, H = a.shape
+    _, N, Ds = V.shape
+    if s.shape != (B, N, H) or w.numel() != H or (gate and (r.shape != (B, T, Ds) or gbias.numel() != Ds)):
+        rest = f"VW{tuple(V.shape)} r{tuple(r.shape)}" if gate else f"w{tuple(w.shape)} sent{tuple(V.shape)}"
+        raise ValueError(f"{what}: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} {rest}")
+    if fam.word_limit:
+        _long_check(what, N)
+    return bf, (a, s, w, V, gbias, r), (B, T, N, H, Ds)
+
+
+def _long_check(what: str, N: int) -> None:
+    nmax = scdm_long_max_words()
+    if N > nmax:
+        raise RuntimeError(f"{what}: N={N} words > {nmax}, the limit of the long-sentence kernels (tsg_scdm_long_max_words)")
+
+
+def _scdm_dtype(bf: bool) -> int:
+    """"f32s" mode: TSG_F32S selects the forward whose P @ sent product runs as split-precision bf16 MFMAs (csrc/scdm_attn.hip)."""
+    return TSG_BF16 if bf else (TSG_F32S if _GEMM_DTYPE == "f32s" else TSG_F32)
+
+
+def _scdm_outputs(like, B, T, N, Ds):
+    """(C or out = [B,T,Ds] in the storage dtype, P = [B,T,N] fp32)."""
+    return torch.empty(B, T, Ds, device=like.device, dtype=like.dtype), torch.empty(B, T, N, device=like.device, dtype=torch.float32)
+
+
+def _scdm_workspace(fam, like, dims, gate: bool):
+    nb = int(getattr(load(), fam.ws_bytes)(*dims, int(gate)))
+    return torch.empty(nb // 4 + 4, device=like.device, dtype=torch.float32), nb
+
+
+def _scdm_backward(fam, dt, a, s, w, V, P, dY, gbias=None, r=None):
+    """(da, ds, dw, dV) of K1, or (da, ds, dw, dVW, dgbias, dr) of K1g when ``gbias`` and ``r`` are given."""
+    gate = r is not None
+    B, T, H = a.shape
+    _, N, Ds = V.shape
+    ws, nb = _scdm_workspace(fam, a, (B, T, N, H, Ds), gate)
+    acts = (a, s, V, dY, r) if gate else (a, s, V, dY)
+    # a bf16 shape only the two-kernel (fp32-storage) backward takes (decided by the library's predicate, not by a failing call):
+    # fp32 copies through it, results rounded to bf16
+    copies = fam.exchange and dt == TSG_BF16 and not scdm_bwd_fused_ok(B, T, N, H, Ds)
+    if copies:
+        acts, dt = tuple(t.float() for t in acts), TSG_F32
+    a, s, V, dY = acts[:4]
+    da, ds, dV, dw = torch.empty_like(a), torch.empty_like(s), torch.empty_like(V), torch.empty_like(w)
+    if fam.exchange and not copies:
+        _gate_before()                              # the partner exchange of the one-launch backward wants its workgroup pairs co-resident
+    if gate:
+        r = acts[4]
+        dgb, dr = torch.empty_like(gbias), torch.empty_like(r)
+        _call(fam.gate_bwd, a, ptr(a), ptr(s), ptr(w), ptr(V), ptr(gbias), ptr(r), ptr(P), ptr(dY),
+              ptr(da), ptr(ds), ptr(dw), ptr(dV), ptr(dgb), ptr(dr), ptr(ws), nb, B, T, N, H, Ds, dt)
+        grads = (da, ds, dV, dr)
+    else:
+        _call(fam.bwd, a, ptr(a), ptr(s), ptr(w), ptr(V), ptr(P), ptr(dY), ptr(da), ptr(ds), ptr(dw), ptr(dV), ptr(ws), nb, B, T, N, H, Ds, dt)
+        grads = (da, ds, dV)
+    if copies:
+        grads = tuple(g.to(_BF) for g in grads)
+    return (grads[0], grads[1], dw, grads[2]) + ((dgb, grads[3]) if gate else ())
+
+
 class _ScdmAttn(torch.autograd.Function):
-    """K1: (a=[B,T,H], s=[B,N,H], w=[H], sent=[B,N,Ds]) -> (C=[B,T,Ds], P=[B,T,N])."""
+    """K1: (a=[B,T,H], s=[B,N,H], w=[H], sent=[B,N,Ds]) -> (C=[B,T,Ds], P=[B,T,N]), by the kernels of ``fam``."""
 
     @staticmethod
     @_fwd
-    def forward(ctx, a, s, w, sent):
+    def forward(ctx, fam, a, s, w, sent):
         require_device(a, s, w, sent)
-        bf = a.dtype == _BF                                    # bf16 storage: a, s, sent, C (and their gradients) as bf16
-        a, s, w, sent = _act(a, bf), _act(s, bf), _f32p(w), _act(sent, bf)
-        B, T, H = a.shape
-        _, N, Ds = sent.shape
-        if s.shape != (B, N, H) or w.numel() != H:
-            raise ValueError(f"scdm_attn: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} w{tuple(w.shape)} sent{tuple(sent.shape)}")
-        C = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
-        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
-        # "f32s" mode: TSG_F32S selects the forward whose P @ sent product runs as split-precision bf16 MFMAs (csrc/scdm_attn.hip)
-        ctx.dt = TSG_BF16 if bf else (TSG_F32S if _GEMM_DTYPE == "f32s" else TSG_F32)
-        _call("tsg_scdm_attn_fwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(C), ptr(P),
-                                       B, T, N, H, Ds, ctx.dt)
+        bf, (a, s, w, sent, _, _), (B, T, N, H, Ds) = _scdm_operands(fam, a, s, w, sent)
+        C, P = _scdm_outputs(a, B, T, N, Ds)
+        ctx.fam, ctx.dt = fam, _scdm_dtype(bf)
+        _call(fam.fwd, a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(C), ptr(P), B, T, N, H, Ds, ctx.dt)
         ctx.save_for_backward(a, s, w, sent, P)
         ctx.mark_non_differentiable(P)
         return C, P
@@ -634,53 +721,21 @@ class _ScdmAttn(torch.autograd.Function):
     @_bwd
     def backward(ctx, dC, _dP):
         a, s, w, sent, P = ctx.saved_tensors
-        dC = _act(dC, ctx.dt == TSG_BF16)
-        B, T, H = a.shape
-        _, N, Ds = sent.shape
-        da = torch.empty_like(a); ds = torch.empty_like(s)
-        dw = torch.empty_like(w); dsent = torch.empty_like(sent)
-        nb = int(load().tsg_scdm_bwd_ws_bytes(B, T, N, H, Ds, 0))
-        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
-        if ctx.dt != TSG_BF16 or scdm_bwd_fused_ok(B, T, N, H, Ds):
-            _gate_before()                          # the partner exchange of the one-launch backward wants its workgroup pairs co-resident
-            _call("tsg_scdm_attn_bwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(P), ptr(dC), ptr(da), ptr(ds),
-                                           ptr(dw), ptr(dsent), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
-        else:
-            # a shape only the two-kernel (fp32-storage) backward takes (decided by the library's predicate, not by a failing
-            # call): fp32 copies through it, results rounded to bf16
-            af, sf, vf, gf = a.float(), s.float(), sent.float(), dC.float()
-            daf, dsf, dvf = torch.empty_like(af), torch.empty_like(sf), torch.empty_like(vf)
-            _call("tsg_scdm_attn_bwd", af, ptr(af), ptr(sf), ptr(w), ptr(vf), ptr(P), ptr(gf), ptr(daf), ptr(dsf),
-                                           ptr(dw), ptr(dvf), ptr(ws), nb, B, T, N, H, Ds, TSG_F32)
-            da, ds, dsent = daf.to(_BF), dsf.to(_BF), dvf.to(_BF)
-        return da, ds, dw, dsent
-
-
-def scdm_attn(a, s, w, sent, return_p: bool = False):
-    """Fused SCDM additive cross-attention on projected inputs (see include/tsg_hip.h, K1)."""
-    C, P = _ScdmAttn.apply(a, s, w.reshape(-1), sent)      # [1,H] Linear weight or [H]: autograd undoes the view
-    return (C, P) if return_p else C
+        return (None,) + _scdm_backward(ctx.fam, ctx.dt, a, s, w, sent, P, _act(dC, ctx.dt == TSG_BF16))
 
 
 class _ScdmGate(torch.autograd.Function):
-    """K1g: (a, s, w, VW=[B,N,Ds], gbias=[Ds], r=[B,T,Ds]) -> out = r * sigmoid(P @ VW + gbias)."""
+    """K1g: (a, s, w, VW=[B,N,Ds], gbias=[Ds], r=[B,T,Ds]) -> out = r * sigmoid(P @ VW + gbias), by the kernels of ``fam``."""
 
     @staticmethod
     @_fwd
-    def forward(ctx, a, s, w, VW, gbias, r, sink=None):
+    def forward(ctx, fam, a, s, w, VW, gbias, r, sink=None):
         require_device(a, s, w, VW, gbias, r)
         ctx.sink, ctx.r_in = sink, (r if sink is not None else None)
-        bf = r.dtype == _BF                                    # bf16 storage: a, s, VW, r, out (and their gradients) as bf16
-        a, s, w, VW, gbias, r = _act(a, bf), _act(s, bf), _f32p(w), _act(VW, bf), _f32p(gbias), _act(r, bf)
-        B, T, H = a.shape
-        _, N, Ds = VW.shape
-        if s.shape != (B, N, H) or w.numel() != H or r.shape != (B, T, Ds) or gbias.numel() != Ds:
-            raise ValueError(f"scdm_gate: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} VW{tuple(VW.shape)} r{tuple(r.shape)}")
-        out = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
-        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
-        ctx.dt = TSG_BF16 if bf else (TSG_F32S if _GEMM_DTYPE == "f32s" else TSG_F32)
-        _call("tsg_scdm_gate_fwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(out), ptr(P),
-              B, T, N, H, Ds, ctx.dt)
+        bf, (a, s, w, VW, gbias, r), (B, T, N, H, Ds) = _scdm_operands(fam, a, s, w, VW, gbias, r)
+        out, P = _scdm_outputs(a, B, T, N, Ds)
+        ctx.fam, ctx.dt = fam, _scdm_dtype(bf)
+        _call(fam.gate_fwd, a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(out), ptr(P), B, T, N, H, Ds, ctx.dt)
         ctx.save_for_backward(a, s, w, VW, gbias, r, P)
         return out
 
@@ -688,32 +743,33 @@ class _ScdmGate(torch.autograd.Function):
     @_bwd
     def backward(ctx, dout):
         a, s, w, VW, gbias, r, P = ctx.saved_tensors
-        dout = _act(dout, ctx.dt == TSG_BF16)
-        B, T, H = a.shape
-        _, N, Ds = VW.shape
-        da = torch.empty_like(a); ds = torch.empty_like(s); dw = torch.empty_like(w)
-        dVW = torch.empty_like(VW); dgb = torch.empty_like(gbias); dr = torch.empty_like(r)
-        nb = int(load().tsg_scdm_bwd_ws_bytes(B, T, N, H, Ds, 1))
-        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
-        if ctx.dt != TSG_BF16 or scdm_bwd_fused_ok(B, T, N, H, Ds):
-            _gate_before()                          # the partner exchange of the one-launch backward wants its workgroup pairs co-resident
-            _call("tsg_scdm_gate_bwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(P), ptr(dout),
-                  ptr(da), ptr(ds), ptr(dw), ptr(dVW), ptr(dgb), ptr(dr), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
-        else:
-            af, sf, vf, rf, gf = a.float(), s.float(), VW.float(), r.float(), dout.float()
-            daf, dsf, dvf, drf = torch.empty_like(af), torch.empty_like(sf), torch.empty_like(vf), torch.empty_like(rf)
-            _call("tsg_scdm_gate_bwd", af, ptr(af), ptr(sf), ptr(w), ptr(vf), ptr(gbias), ptr(rf), ptr(P), ptr(gf),
-                  ptr(daf), ptr(dsf), ptr(dw), ptr(dvf), ptr(dgb), ptr(drf), ptr(ws), nb, B, T, N, H, Ds, TSG_F32)
-            da, ds, dVW, dr = daf.to(_BF), dsf.to(_BF), dvf.to(_BF), drf.to(_BF)
+        da, ds, dw, dVW, dgb, dr = _scdm_backward(ctx.fam, ctx.dt, a, s, w, VW, P, _act(dout, ctx.dt == TSG_BF16), gbias, r)
         if ctx.sink is not None and ctx.sink.tensor is not None and dr.dtype == ctx.sink.tensor.dtype:
             _sink_add(ctx.sink, ctx.r_in, dr)                  # r is a shared activation (the BiLSTM output: also W_a's input): its gradient meets the other there
             dr = None
-        return da, ds, dw, dVW, dgb, dr, None
+        return None, da, ds, dw, dVW, dgb, dr, None
+
+
+def scdm_attn(a, s, w, sent, return_p: bool = False):
+    """Fused SCDM additive cross-attention on projected inputs (see include/tsg_hip.h, K1)."""
+    C, P = _ScdmAttn.apply(_K1, a, s, w.reshape(-1), sent)      # [1,H] Linear weight or [H]: autograd undoes the view
+    return (C, P) if return_p else C
 
 
 def scdm_gate(a, s, w, VW, gbias, r):
     """SCDM attention fused with the recalibration gate (see include/tsg_hip.h, K1g)."""
-    return _ScdmGate.apply(a, s, w.reshape(-1), VW, gbias, r, _sink_for(r))
+    return _ScdmGate.apply(_K1, a, s, w.reshape(-1), VW, gbias, r, _sink_for(r))
+
+
+def scdm_attn_long(a, s, w, sent, return_p: bool = False):
+    """``scdm_attn`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
+    C, P = _ScdmAttn.apply(_K1L, a, s, w.reshape(-1), sent)
+    return (C, P) if return_p else C
+
+
+def scdm_gate_long(a, s, w, VW, gbias, r):
+    """``scdm_gate`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
+    return _ScdmGate.apply(_K1L, a, s, w.reshape(-1), VW, gbias, r, _sink_for(r))
 
 
 class _ScdmGateProj(torch.autograd.Function):
@@ -734,8 +790,7 @@ class _ScdmGateProj(torch.autograd.Function):
         if wa.shape[1] != Dv or s.shape != (B, N, H) or w.numel() != H or Ds != Dv or gbias.numel() != Ds:
             raise ValueError(f"scdm_gate_proj: shape mismatch x{tuple(x.shape)} W_a{tuple(wa.shape)} s{tuple(s.shape)} VW{tuple(VW.shape)}")
         a = gemm_f32s(x.view(B * T, Dv), wa).view(B, T, H)
-        out = torch.empty(B, T, Ds, device=x.device, dtype=torch.float32)
-        P = torch.empty(B, T, N, device=x.device, dtype=torch.float32)
+        out, P = _scdm_outputs(x, B, T, N, Ds)
         _call("tsg_scdm_gate_fwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(x), ptr(out), ptr(P), B, T, N, H, Ds, TSG_F32S)
         ctx.save_for_backward(x, wa, a, s, w, VW, gbias, P)
         return out
@@ -744,17 +799,9 @@ class _ScdmGateProj(torch.autograd.Function):
     @_bwd
     def backward(ctx, dout):
         x, wa, a, s, w, VW, gbias, P = ctx.saved_tensors
-        dout = _f32c(dout)
         B, T, Dv = x.shape
         H = wa.shape[0]
-        _, N, Ds = VW.shape
-        da = torch.empty_like(a); ds = torch.empty_like(s); dw = torch.empty_like(w)
-        dVW = torch.empty_like(VW); dgb = torch.empty_like(gbias); dx = torch.empty_like(x)
-        nb = int(load().tsg_scdm_bwd_ws_bytes(B, T, N, H, Ds, 1))
-        ws = torch.empty(nb // 4 + 4, device=x.device, dtype=torch.float32)
-        _gate_before()
-        _call("tsg_scdm_gate_bwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(x), ptr(P), ptr(dout),
-              ptr(da), ptr(ds), ptr(dw), ptr(dVW), ptr(dgb), ptr(dx), ptr(ws), nb, B, T, N, H, Ds, TSG_F32S)      # dx <- dr
+        da, ds, dw, dVW, dgb, dx = _scdm_backward(_K1, TSG_F32S, a, s, w, VW, P, _f32c(dout), gbias, x)               # dx <- dr
         da2, x2 = da.view(B * T, H), x.view(B * T, Dv)
         dwa = None
         if ctx.needs_input_grad[1]:
@@ -789,109 +836,6 @@ def scdm_long_max_words() -> int:
 def scdm_long_ok(N: int, H: int, Ds: int) -> bool:
     """Shapes ``scdm_attn_long`` / ``scdm_gate_long`` take, in every storage dtype (the library's own planner, not a failing call)."""
     return int(load().tsg_scdm_long_ws_bytes(1, 1, N, H, Ds, 1)) > 0
-
-
-def _long_dtype(bf: bool) -> int:
-    return TSG_BF16 if bf else (TSG_F32S if _GEMM_DTYPE == "f32s" else TSG_F32)
-
-
-def _long_check(what: str, N: int, H: int, Ds: int) -> None:
-    nmax = scdm_long_max_words()
-    if N > nmax:
-        raise RuntimeError(f"{what}: N={N} words > {nmax}, the limit of the long-sentence kernels (tsg_scdm_long_max_words)")
-
-
-class _ScdmAttnLong(torch.autograd.Function):
-    """K1 for up to 128 words (tsg_scdm_long_*): (a=[B,T,H], s=[B,N,H], w=[H], sent=[B,N,Ds]) -> (C=[B,T,Ds], P=[B,T,N]).
-    The bf16 kernels take every shape the fp32 ones take, so no shape goes through fp32 copies; the backward's five launches
-    exchange nothing between workgroups, so no co-residency gate is asked for."""
-
-    @staticmethod
-    @_fwd
-    def forward(ctx, a, s, w, sent):
-        require_device(a, s, w, sent)
-        bf = a.dtype == _BF
-        a, s, w, sent = _act(a, bf), _act(s, bf), _f32p(w), _act(sent, bf)
-        B, T, H = a.shape
-        _, N, Ds = sent.shape
-        if s.shape != (B, N, H) or w.numel() != H:
-            raise ValueError(f"scdm_attn_long: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} w{tuple(w.shape)} sent{tuple(sent.shape)}")
-        _long_check("scdm_attn_long", N, H, Ds)
-        C = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
-        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
-        ctx.dt = _long_dtype(bf)
-        _call("tsg_scdm_long_fwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(C), ptr(P), B, T, N, H, Ds, ctx.dt)
-        ctx.save_for_backward(a, s, w, sent, P)
-        ctx.mark_non_differentiable(P)
-        return C, P
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dC, _dP):
-        a, s, w, sent, P = ctx.saved_tensors
-        dC = _act(dC, ctx.dt == TSG_BF16)
-        B, T, H = a.shape
-        _, N, Ds = sent.shape
-        da = torch.empty_like(a); ds = torch.empty_like(s)
-        dw = torch.empty_like(w); dsent = torch.empty_like(sent)
-        nb = int(load().tsg_scdm_long_ws_bytes(B, T, N, H, Ds, 0))
-        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
-        _call("tsg_scdm_long_bwd", a, ptr(a), ptr(s), ptr(w), ptr(sent), ptr(P), ptr(dC), ptr(da), ptr(ds),
-              ptr(dw), ptr(dsent), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
-        return da, ds, dw, dsent
-
-
-def scdm_attn_long(a, s, w, sent, return_p: bool = False):
-    """``scdm_attn`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
-    C, P = _ScdmAttnLong.apply(a, s, w.reshape(-1), sent)
-    return (C, P) if return_p else C
-
-
-class _ScdmGateLong(torch.autograd.Function):
-    """K1g for up to 128 words: (a, s, w, VW=[B,N,Ds], gbias=[Ds], r=[B,T,Ds]) -> out = r * sigmoid(P @ VW + gbias)."""
-
-    @staticmethod
-    @_fwd
-    def forward(ctx, a, s, w, VW, gbias, r, sink=None):
-        require_device(a, s, w, VW, gbias, r)
-        ctx.sink, ctx.r_in = sink, (r if sink is not None else None)
-        bf = r.dtype == _BF
-        a, s, w, VW, gbias, r = _act(a, bf), _act(s, bf), _f32p(w), _act(VW, bf), _f32p(gbias), _act(r, bf)
-        B, T, H = a.shape
-        _, N, Ds = VW.shape
-        if s.shape != (B, N, H) or w.numel() != H or r.shape != (B, T, Ds) or gbias.numel() != Ds:
-            raise ValueError(f"scdm_gate_long: shape mismatch a{tuple(a.shape)} s{tuple(s.shape)} VW{tuple(VW.shape)} r{tuple(r.shape)}")
-        _long_check("scdm_gate_long", N, H, Ds)
-        out = torch.empty(B, T, Ds, device=a.device, dtype=a.dtype)
-        P = torch.empty(B, T, N, device=a.device, dtype=torch.float32)
-        ctx.dt = _long_dtype(bf)
-        _call("tsg_scdm_long_gate_fwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(out), ptr(P),
-              B, T, N, H, Ds, ctx.dt)
-        ctx.save_for_backward(a, s, w, VW, gbias, r, P)
-        return out
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dout):
-        a, s, w, VW, gbias, r, P = ctx.saved_tensors
-        dout = _act(dout, ctx.dt == TSG_BF16)
-        B, T, H = a.shape
-        _, N, Ds = VW.shape
-        da = torch.empty_like(a); ds = torch.empty_like(s); dw = torch.empty_like(w)
-        dVW = torch.empty_like(VW); dgb = torch.empty_like(gbias); dr = torch.empty_like(r)
-        nb = int(load().tsg_scdm_long_ws_bytes(B, T, N, H, Ds, 1))
-        ws = torch.empty(nb // 4 + 4, device=a.device, dtype=torch.float32)
-        _call("tsg_scdm_long_gate_bwd", a, ptr(a), ptr(s), ptr(w), ptr(VW), ptr(gbias), ptr(r), ptr(P), ptr(dout),
-              ptr(da), ptr(ds), ptr(dw), ptr(dVW), ptr(dgb), ptr(dr), ptr(ws), nb, B, T, N, H, Ds, ctx.dt)
-        if ctx.sink is not None and ctx.sink.tensor is not None and dr.dtype == ctx.sink.tensor.dtype:
-            _sink_add(ctx.sink, ctx.r_in, dr)                  # r is a shared activation: its gradient meets W_a's there, as in _ScdmGate
-            dr = None
-        return da, ds, dw, dVW, dgb, dr, None
-
-
-def scdm_gate_long(a, s, w, VW, gbias, r):
-    """``scdm_gate`` for sentences of up to ``scdm_long_max_words()`` words (see include/tsg_hip.h, K1L)."""
-    return _ScdmGateLong.apply(a, s, w.reshape(-1), VW, gbias, r, _sink_for(r))
 
 
 _k3_ws = {}        # (device, stream, B, T, Hm) -> uint8 workspace of the one-launch K3 backward; its ticket counters are zero between calls

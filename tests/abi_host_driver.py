@@ -54,6 +54,11 @@ def run_checks(lib):
     eq(lib.tsg_scdm_attn_fwd(None, p, p, p, p, p, 1, 1, 1, 4, 4, TSG_F32, None), -1, "NULL")
     assert b"NULL" in lib.tsg_last_error()
     eq(lib.tsg_scdm_attn_fwd(p, p, p, p, p, p, 1, 1, 33, 4, 4, TSG_F32, None), -2, "N > 32")
+    eq(lib.tsg_scdm_attn_fwd(p, p, p, p, None, p, 1, 1, 33, 6, 4, 7, None), -1, "wrong four ways: the NULL pointer is reported")
+    assert b"NULL" in lib.tsg_last_error()
+    eq(lib.tsg_scdm_gate_bwd(*([p] * 15), 1 << 40, 1, 1, 33, 6, 4, 7, None), -4, "dtype, N > 32 and H % 4: the dtype is reported")
+    eq(lib.tsg_scdm_attn_bwd(*([p] * 11), 1 << 40, 1, 1, 33, 6, 4, TSG_F32, None), -2, "N > 32 and H % 4: N is reported")
+    assert b"N=33" in lib.tsg_last_error()
     eq(lib.tsg_scdm_attn_fwd(p, p, p, p, p, p, 1, 1, 1, 6, 4, TSG_F32, None), -3, "H % 4")
     eq(lib.tsg_scdm_attn_fwd(p, p, p, p, p, p, 1, 1, 1, 4, 4, 7, None), -4, "dtype")
     eq(lib.tsg_scdm_attn_fwd(p + 4, p, p, p, p, p, 1, 1, 1, 4, 4, TSG_F32, None), -3, "misaligned")

@@ -44,6 +44,8 @@ def run_checks(lib):
         eq(call(ok, (1, 1, 0, 8, 8)), E_SHAPE, f"{name} N=0")
         eq(call(ok, (1, 1, nmax + 1, 8, 8)), E_SHAPE, f"{name} N=NMAX+1")
         assert f"N={nmax + 1}".encode() in lib.tsg_last_error(), lib.tsg_last_error()
+        eq(call([None] + ok[1:], (1, 1, nmax + 1, 8, 8)), E_NULL, f"{name} NULL and N=NMAX+1")    # wrong twice: the pointer check comes first
+        assert b"NULL" in lib.tsg_last_error()
         for dims in ((0, 1, 40, 8, 8), (1, 0, 40, 8, 8), (1, 1, 40, 0, 8), (1, 1, 40, 8, 0), (-2, 1, 40, 8, 8), (1, 1, -40, 8, 8)):
             eq(call(ok, dims), E_SHAPE, f"{name} dims {dims}")
         eq(call(ok, good, 7), E_DTYPE, f"{name} dtype 7")
@@ -78,6 +80,8 @@ def run_checks(lib):
     eq(lib.tsg_scdm_attn_fwd(p, p, p, p, p, p, 1, 1, 33, 4, 4, TSG_F32, None), E_SHAPE, "tsg_scdm_attn_fwd N=33")
     assert b"N=33" in lib.tsg_last_error()
     eq(lib.tsg_scdm_gate_fwd(p, p, p, p, p, p, p, p, 1, 1, 33, 4, 4, TSG_F32, None), E_SHAPE, "tsg_scdm_gate_fwd N=33")
+    eq(lib.tsg_scdm_attn_fwd(None, p, p, p, p, p, 1, 1, 33, 4, 4, TSG_F32, None), E_NULL, "tsg_scdm_attn_fwd NULL and N=33")
+    assert b"NULL" in lib.tsg_last_error()
     eq(lib.tsg_scdm_bwd_ws_bytes(1, 1, 33, 4, 4, 0), 0, "tsg_scdm_bwd_ws_bytes N=33")
     return n[0]
 
