@@ -204,7 +204,12 @@ int tsg_mha_fwd(const void* Q, const void* K, const void* V, void* O, void* A_su
  * S_sum side outputs are requested; otherwise the exact kernels.
  * dtype TSG_BF16: Q, K, V, O (and dO, dQ, dK, dV) are bf16, lse / delta_ws fp32 -- the split-precision kernels with 2-byte
  * elements (half the HBM bytes; the lo operand planes are zero).  Needs d_key == d_value, no A_sum / S_sum, head widths 32 .. 256
- * in steps of 32 in tsg_mha_fwd and 32 .. 128 in tsg_mha_bwd (TSG_E_SHAPE otherwise).                                           */
+ * in steps of 32 in tsg_mha_fwd and 32 .. 128 in tsg_mha_bwd (TSG_E_SHAPE otherwise).
+ * Split-precision backward with one key block no wider than the head (Tk <= 128 and Tk <= head width, where the fused one-tile
+ * kernel does not run): dS is written ONCE, in the storage type, into dQ's buffer, and dQ = dS K is formed from it in place.
+ * With bf16 storage dS is therefore rounded to bf16 before that product: a relative 2^-9 per element of dS, on top of dQ's own
+ * output rounding (the dK/dV + dQ pair, TSG_K2_BWD=pair, contracts dS from registers).  On every path dQ must be a buffer of its
+ * own with row stride d_key that aliases none of Q, K, V, dO.                                                                    */
 int tsg_mha_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* lse,
                 void* dQ, void* dK, void* dV, void* delta_ws, int B, int Tq, int Tk, int d_key, int d_value,
                 int n_heads, float scale, int causal, float p_drop, uint64_t seed, uint64_t offset, int dtype,

@@ -31,6 +31,7 @@ constexpr int LS = CC + 4;      // padded LDS row stride (floats)
 constexpr int PS = KB + 4;      // padded stride of the P / dS tiles
 constexpr int MAXVC = 4;        // head width of V <= MAXVC*CC = 512
 constexpr float kNegBig = -3.0e38f;
+constexpr size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }        // (host side: LDS byte counts)
 
 // Attention dropout (reference: out = dropout(softmax(A)) V, attention.py:53-54; the returned A_softmax is the
 // un-dropped softmax).  Counter-based: the keep decision of element (b, head, q, key) is a hash of its index and
@@ -402,6 +403,9 @@ __global__ __launch_bounds__(kMfmaThreads) __attribute__((amdgpu_waves_per_eu(2,
   }
 }
 
+// dynamic LDS bytes of mha_fwd_mfma_kernel: a key tile, or the Q / O stage of QB rows (KS, VS: the row strides the host passes)
+inline size_t fwd_mfma_lds(int KS, int VS) { return sizeof(float) * max_sz((size_t)32 * (KS + VS), max_sz((size_t)QB * KS, (size_t)QB * VS)); }
+
 // ------------------------------------------------------------------------------------------
 // forward, MFMA path for WIDE heads (128 < head width <= 256: Self_Attention_predictor at d = 1024 has 2d/8 = 256 channels
 // per head, SpanPredictor.py:244-266).  Keeping a 256-wide Q fragment and a 256-wide O accumulator per lane as the kernel
@@ -546,6 +550,11 @@ __global__ __launch_bounds__(kWideThreads) void mha_fwd_mfma_wide_kernel(
     if (qq < Tq)
       *reinterpret_cast<float4*>(O + ((size_t)b * Tq + qq) * dv + hd * dvh + c) = *reinterpret_cast<const float4*>(Ol + r * VS + c);
   }
+}
+
+// dynamic LDS bytes of mha_fwd_mfma_wide_kernel: a key tile + the waves' exchange area, or the Q / O stage of QBW rows
+inline size_t fwd_mfma_wide_lds(int KS, int VS) {
+  return sizeof(float) * max_sz((size_t)32 * (KS + VS) + 2 * 4 * 16 * 64, max_sz((size_t)QBW * KS, (size_t)QBW * VS));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -893,6 +902,9 @@ __global__ __launch_bounds__(kMfmaThreads) void mha_bwd_mfma_kernel(
   }
 }
 
+// dynamic LDS bytes of mha_bwd_mfma_kernel (KS, VS2: the row strides the host passes)
+inline size_t bwd_mfma_lds(int KS, int VS2) { return sizeof(float) * ((size_t)64 * (KS + VS2) + 2 * 4 * 16 * 64 + 32 * 66 + 64); }
+
 // ------------------------------------------------------------------------------------------
 // backward, MFMA path for WIDE heads (128 < head width <= 256).  Same scheme as above with TWO 32-channel tiles per
 // wave (wave w owns channels [64w, 64w+64) of every product).  Four [32][258] operand tiles do not fit the LDS next to
@@ -1061,6 +1073,9 @@ __global__ __launch_bounds__(kMfmaThreads) void mha_bwd_mfma_wide_kernel(
     }
   }
 }
+
+// dynamic LDS bytes of mha_bwd_mfma_wide_kernel (KS, VS2: the row strides the host passes)
+inline size_t bwd_mfma_wide_lds(int KS, int VS2) { return sizeof(float) * ((size_t)32 * (2 * KS + VS2) + 2 * 4 * 16 * 64 + 32 * 66 + 64); }
 
 // ------------------------------------------------------------------------------------------
 // backward in SPLIT PRECISION (dtype TSG_F32S; head widths 32 / 64 / 96 / 128, d_key == d_value): the five products of the
@@ -1416,6 +1431,9 @@ __global__ __launch_bounds__(256) void mha_bwd_split_dkv_kernel(
 #endif
 }
 
+// LDS bytes of mha_bwd_split_dkv_kernel: two buffers of two (row-major + transposed) tiles + delta of 128 rows
+template <int DT> constexpr size_t bwd_dkv_lds() { return sizeof(unsigned) * 2 * 2 * SplitTile<DT, true>::kDwords + sizeof(float) * 128; }
+
 // (B') dQ = dS K from the dS the WDS kernel left in the dQ buffer, IN PLACE: grid = B * H * ceil(Tq / 128); wave w owns queries qb + 32 w .. +31,
 // reads its 32 dS rows (the head's columns) into A-operand fragments before anything is stored, streams the head's K rows through LDS as
 // transposed bf16 planes (32 keys per tile) and writes its 32 dQ rows over the dS rows it read.  2 DT x DT x 3 MFMAs per tile and wave; no S, no
@@ -1467,6 +1485,9 @@ __global__ __launch_bounds__(256) void mha_bwd_dq_from_ds_kernel(const ET* __res
       if (q < Tq) st1(dQb + (size_t)q * dk + 32 * ct + jl, dqt[ct][r]);
     }
 }
+
+// LDS bytes of mha_bwd_dq_from_ds_kernel: two buffers of transposed K planes
+template <int DT> constexpr size_t bwd_dq_from_ds_lds() { return sizeof(unsigned) * 2 * SplitTile<DT, true, false>::kDwords; }
 
 // delta[b][h][q] = <dO[b,q,head], O[b,q,head]> for either storage type (one wave per (b, q) row)
 template <typename ET>
@@ -1582,6 +1603,13 @@ __global__ __launch_bounds__(256) void mha_bwd_split_dq_kernel(
     const int qq = qb + 32 * wv + r;
     if (qq < Tq) st4(dQb + (size_t)qq * dk + c, *reinterpret_cast<const float4*>(Ol + r * OP + c));
   }
+}
+
+// LDS bytes of the four waves' [32][32 DT + 4] fp32 output blocks (the OP pitch of this kernel, the forward and the one-tile kernel),
+// and of mha_bwd_split_dq_kernel: two buffers of K (row-major + transposed) + V (row-major) planes, reused as those blocks
+template <int DT> constexpr size_t split_out_lds() { return sizeof(float) * 4 * 32 * (32 * DT + 4); }
+template <int DT> constexpr size_t bwd_dq_lds() {
+  return max_sz(sizeof(unsigned) * 2 * (SplitTile<DT, true>::kDwords + SplitTile<DT, false>::kDwords), split_out_lds<DT>());
 }
 
 // ---- wide heads (160 .. 256 channels) in the backward: at width 256 a 32-row wave's own rows are 128 registers per tensor, and two
@@ -1858,24 +1886,9 @@ __global__ __launch_bounds__(256) void mha_bwd_split_dkv_wide_kernel(
     }
 }
 
-template <int DT, bool DROP>
-int launch_bwd_split_wide(const char* fn, const float* Q, const float* K, const float* V, const float* O, const float* dO, const float* lse,
-                          float* delta, float* dQ, float* dK, float* dV, int B, int Tq, int Tk, int dk, int H, float inv_scale,
-                          int causal, const DropCfg& dc, hipStream_t st) {
-  using SR = SplitTile<DT, false>;
-  size_t lds = sizeof(unsigned) * (size_t)(2 * SR::kDwords) + sizeof(float) * (4 * 2 * 16 * 64 + 64);
-  const size_t outb = sizeof(float) * 4 * 32 * 132;
-  if (outb > lds) lds = outb;
-  auto ka = mha_bwd_split_dkv_wide_kernel<DT, DROP>;
-  auto kq = mha_bwd_split_dq_wide_kernel<DT, DROP>;
-  hipError_t e = allow_lds(ka, lds);                       // (device, kernel)-keyed table: cheap when already set
-  if (e == hipSuccess) e = allow_lds(kq, lds);
-  if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-  hipLaunchKernelGGL(kq, dim3(B * H * cdiv(Tq, 64)), dim3(256), lds, st, Q, K, V, dO, lse, O, delta, dQ, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-  int rc = check_launch(fn);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ka, dim3(B * H * cdiv(Tk, 64)), dim3(256), lds, st, Q, K, V, dO, lse, (const float*)delta, dK, dV, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-  return check_launch(fn);
+// LDS bytes of the two wide kernels: two buffers of row-major planes + the wave pairs' exchange area, reused as [4][32][132] output blocks
+template <int DT> constexpr size_t bwd_wide_lds() {
+  return max_sz(sizeof(unsigned) * 2 * SplitTile<DT, false>::kDwords + sizeof(float) * (4 * 2 * 16 * 64 + 64), sizeof(float) * 4 * 32 * 132);
 }
 
 // Forward in split precision (dtype TSG_F32S, no A_forward side outputs; same shapes as the backward): the dQ kernel's structure with
@@ -1984,19 +1997,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT <= 4 ? 2
   }
 }
 
-template <int DT, bool DROP, typename ET = float>
-int launch_fwd_split(const char* fn, const ET* Q, const ET* K, const ET* V, ET* O, float* lse, int B, int Tq, int Tk, int dk,
-                     int H, float inv_scale, int causal, const DropCfg& dc, hipStream_t st) {
-  using SK = SplitTile<DT, false>;
-  using SV = SplitTile<DT, true, false>;
-  size_t lds = sizeof(unsigned) * (size_t)(2 * (SK::kDwords + SV::kDwords));
-  const size_t outb = sizeof(float) * 4 * 32 * (32 * DT + 4);
-  if (outb > lds) lds = outb;
-  auto kf = mha_fwd_split_kernel<DT, DROP, ET>;
-  hipError_t e = allow_lds(kf, lds);
-  if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-  hipLaunchKernelGGL(kf, dim3(B * H * cdiv(Tq, 128)), dim3(256), lds, st, Q, K, V, O, lse, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-  return check_launch(fn);
+// LDS bytes of mha_fwd_split_kernel: two buffers of its K (row-major) + V (transposed) planes, reused as the four waves' output blocks
+template <int DT> constexpr size_t fwd_split_lds() {
+  return max_sz(sizeof(unsigned) * 2 * (SplitTile<DT, false>::kDwords + SplitTile<DT, true, false>::kDwords), split_out_lds<DT>());
 }
 
 // (C) backward for ONE key tile (Tk <= 32: cross attention over the T_word <= 32 words of a query) -- one kernel, every input read
@@ -2190,67 +2193,222 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-template <int DT, bool DROP, typename ET = float>
-int launch_bwd_split(const char* fn, const ET* Q, const ET* K, const ET* V, const ET* O, const ET* dO, const float* lse,
-                     float* delta, ET* dQ, ET* dK, ET* dV, int B, int Tq, int Tk, int dk, int H, float inv_scale,
-                     int causal, const DropCfg& dc, hipStream_t st) {
-  using ST = SplitTile<DT, true>;
-  using SV = SplitTile<DT, false>;
-  // one key tile: the fused kernel (bf16 outputs cannot take the float atomics several query blocks add with: those run the pair)
-  if (Tk <= 32 && (!storage_is_bf16<ET>::value || Tq <= 128)) {
-    size_t lds_c = sizeof(unsigned) * (size_t)(ST::kDwords + SV::kDwords) + sizeof(float) * 128;
-    const size_t out_c = sizeof(float) * 4 * 32 * (32 * DT + 4);
-    if (out_c > lds_c) lds_c = out_c;
-    const int qblocks = cdiv(Tq, 128);
-    auto kc = mha_bwd_split_cross_kernel<DT, DROP, ET>;
-    hipError_t e = allow_lds(kc, lds_c);          // table hit (no runtime call) after the first, eager, launch on this device
-    if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    if (qblocks > 1) {                                                     // several query blocks add into dK / dV
-      const size_t nb = sizeof(float) * (size_t)B * Tk * dk;
-      e = zero_async(dK, nb, st);
-      if (e == hipSuccess) e = zero_async(dV, nb, st);
-      if (e != hipSuccess) return set_error((int)e, "%s: zero fill: %s", fn, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kc, dim3(B * H * qblocks), dim3(256), lds_c, st, Q, K, V, dO, lse, O, dQ, dK, dV, B, Tq, Tk, dk, H, inv_scale,
-                       causal, qblocks > 1 ? 1 : 0, dc);
-    return check_launch(fn);
-  }
-  const size_t lds_a = sizeof(unsigned) * (size_t)(2 * 2 * ST::kDwords) + sizeof(float) * 128;
-  // one key block no wider than the head (self-attention over T <= 128 clips at head width 128: the north-star shape): dS is written once and
-  // dQ = dS K is a small product over it -- Q, K, V, dO are read ONCE (round-5 review item 6).  TSG_K2_BWD=pair keeps the two full kernels (A/B timing).
-  static const bool pair_only = [] { const char* e = getenv("TSG_K2_BWD"); return e && e[0] == 'p'; }();
-  if (Tk <= 128 && Tk <= 32 * DT && !pair_only) {
-    using SKT = SplitTile<DT, true, false, ET>;
-    const size_t lds_q = sizeof(unsigned) * (size_t)(2 * SKT::kDwords);
-    auto kd = mha_bwd_delta_t_kernel<ET>;
-    auto kw = mha_bwd_split_dkv_kernel<DT, DROP, ET, true>;
-    auto kx = mha_bwd_dq_from_ds_kernel<DT, ET>;
-    hipError_t e = allow_lds(kw, lds_a);
-    if (e == hipSuccess) e = allow_lds(kx, lds_q);
-    if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(kd, dim3(cdiv(B * Tq, 4)), dim3(256), 0, st, O, dO, delta, B, Tq, dk, H);
-    hipLaunchKernelGGL(kw, dim3(B * H), dim3(256), lds_a, st, Q, K, V, dO, lse, (const float*)delta, dK, dV, dQ, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-    int rc = check_launch(fn);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kx, dim3(B * H * cdiv(Tq, 128)), dim3(256), lds_q, st, K, dQ, B, Tq, Tk, dk, H);
-    return check_launch(fn);
-  }
-  size_t lds_b = sizeof(unsigned) * (size_t)(2 * (ST::kDwords + SV::kDwords));
-  const size_t out_b = sizeof(float) * 4 * 32 * (32 * DT + 4);
-  if (out_b > lds_b) lds_b = out_b;
-  auto ka = mha_bwd_split_dkv_kernel<DT, DROP, ET>;
-  auto kq = mha_bwd_split_dq_kernel<DT, DROP, ET>;
-  hipError_t e = allow_lds(ka, lds_a);
-  if (e == hipSuccess) e = allow_lds(kq, lds_b);
-  if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-  // dQ first: it also writes delta = <dO, O>, which the dK/dV kernel reads
-  hipLaunchKernelGGL(kq, dim3(B * H * cdiv(Tq, 128)), dim3(256), lds_b, st, Q, K, V, dO, lse, O, delta, dQ, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-  int rc = check_launch(fn);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ka, dim3(B * H * cdiv(Tk, 128)), dim3(256), lds_a, st, Q, K, V, dO, lse, (const float*)delta, dK, dV, (ET*)nullptr, B, Tq, Tk, dk, H, inv_scale, causal, dc);
-  return check_launch(fn);
+// LDS bytes of mha_bwd_split_cross_kernel: the K (row-major + transposed) and V (row-major) planes + delta of the 128 queries,
+// reused as the four waves' output blocks
+template <int DT> constexpr size_t bwd_cross_lds() {
+  return max_sz(sizeof(unsigned) * (SplitTile<DT, true>::kDwords + SplitTile<DT, false>::kDwords) + sizeof(float) * 128, split_out_lds<DT>());
 }
 
+// ------------------------------------------------------------------------------------------
+// host-side dispatch
+// ------------------------------------------------------------------------------------------
+
+// DT = head width / 32 as a template argument, four widths per switch (FIRST = 1: DT 1..4, FIRST = 5: DT 5..8), so that a call site
+// names exactly the instantiations that exist: split forward DT 1..8, split backward 1..4, wide split backward 5..8.
+#define TSG_DISPATCH_DT(DTV, FIRST, CALL)                               \
+  switch (DTV) {                                                        \
+    case FIRST: { constexpr int DT = FIRST; return CALL; }              \
+    case FIRST + 1: { constexpr int DT = FIRST + 1; return CALL; }      \
+    case FIRST + 2: { constexpr int DT = FIRST + 2; return CALL; }      \
+    default: { constexpr int DT = FIRST + 3; return CALL; }             \
+  }
+
+// K2's environment switches, read once per process (A/B timing):
+//   TSG_MHA_SPLIT=<n>  split  atoi of the value, default 1; 0: dtype TSG_F32S runs the exact fp32 kernels, forward and backward
+//                             (TSG_BF16 has no exact form and is not affected)
+//   TSG_K2_BWD=p..     pair   the dK/dV + dQ pair where dS-once would run
+struct K2Env { bool split, pair; };
+const K2Env& k2_env() {
+  static const K2Env env = [] {
+    const char* s = getenv("TSG_MHA_SPLIT");
+    const char* b = getenv("TSG_K2_BWD");
+    return K2Env{(s ? atoi(s) : 1) != 0, b && b[0] == 'p'};
+  }();
+  return env;
+}
+
+// The split kernels' shape condition: equal key / value head widths, a multiple of 32, at most max_width.  The limits by name
+// (functional.mha_bf16_ok restates the bf16 storage ones: forward AND backward, i.e. kSplitBwdMax):
+constexpr int kSplitFwdMax = 256;        // mha_fwd_split_kernel, fp32 and bf16 storage
+constexpr int kSplitBwdMax = 128;        // cross / dS-once / pair, fp32 and bf16 storage
+constexpr int kSplitBwdWideMax = 256;    // 129 .. 256: the wide pair, fp32 storage (TSG_F32S) only
+bool split_widths_ok(int dh, int dvh, int max_width) { return dh == dvh && dh % 32 == 0 && dh <= max_width; }
+
+struct SplitLds { size_t fwd, cross, dkv, dq, dq_from_ds, wide; };
+template <int DT> constexpr SplitLds split_lds() {
+  return {fwd_split_lds<DT>(), bwd_cross_lds<DT>(), bwd_dkv_lds<DT>(), bwd_dq_lds<DT>(), bwd_dq_from_ds_lds<DT>(), bwd_wide_lds<DT>()};
+}
+constexpr SplitLds kSplitLds[9] = {{}, split_lds<1>(), split_lds<2>(), split_lds<3>(), split_lds<4>(),
+                                   split_lds<5>(), split_lds<6>(), split_lds<7>(), split_lds<8>()};
+
+struct Launch { int grid, threads; size_t lds; };        // grid 0: no such launch
+struct K2Args { const char* fn; int B, Tq, Tk, dk, dv, H; float inv_scale; int causal; DropCfg dc; hipStream_t st; };
+struct FwdArgs : K2Args { const void *Q, *K, *V; void *O, *A_sum, *S_sum, *lse; };
+struct BwdArgs : K2Args { const void *Q, *K, *V, *O, *dO, *lse; void *dQ, *dK, *dV, *delta; };
+
+// Which forward kernel a shape gets.  SPLIT: the bf16 hi/lo products, for TSG_BF16 always (the entry point has rejected every
+// other bf16 shape) and for TSG_F32S unless TSG_MHA_SPLIT=0.  The A_forward maps come from the VALU kernel only.
+struct FwdPlan { enum Kind { SPLIT, MFMA, MFMA_WIDE, VALU } kind; int DT; Launch k; int qblocks, KS, VS; };
+FwdPlan plan_fwd(int dtype, bool maps, int B, int Tq, int dh, int dvh, int H) {
+  const bool split = dtype == TSG_BF16 || (dtype == TSG_F32S && k2_env().split);
+  if (!maps && split && split_widths_ok(dh, dvh, kSplitFwdMax))
+    return {FwdPlan::SPLIT, dh / 32, {B * H * cdiv(Tq, 128), 256, kSplitLds[dh / 32].fwd}, 0, 0, 0};
+  if (!maps && dh <= DHMAX && dvh <= DHMAX) {
+    const int KS = roundup(dh, 64) + 2, VS = roundup(dvh, 32) + 4, qb = cdiv(Tq, QB);
+    return {FwdPlan::MFMA, 0, {B * qb * H, kMfmaThreads, fwd_mfma_lds(KS, VS)}, qb, KS, VS};
+  }
+  if (!maps && dh <= DHW && dvh <= DHW) {                  // channels split over the waves
+    const int KS = DHW + 2, VS = DHW + 4, qb = cdiv(Tq, QBW);
+    return {FwdPlan::MFMA_WIDE, 0, {B * qb * H, kWideThreads, fwd_mfma_wide_lds(KS, VS)}, qb, KS, VS};
+  }
+  return {FwdPlan::VALU, 0, {B * cdiv(Tq, TQ), kThreads, 0}, cdiv(Tq, TQ), 0, 0};
+}
+
+// Which backward kernels a shape gets; the launches run in the order delta, a, b.
+//   SPLIT_CROSS    one key tile: the fused kernel (a).  zero_fill: several query blocks add into dK / dV with float atomics
+//   SPLIT_DS_ONCE  one key block no wider than the head: delta pre-pass, dK/dV writing dS into dQ's buffer (a), dQ = dS K (b)
+//   SPLIT_PAIR     dQ, which also writes delta (a), then dK/dV (b)
+//   SPLIT_WIDE     the same pair for head widths 129 .. 256 (channel halves per wave pair), fp32 storage only
+//   MFMA[_WIDE]    exact fp32: delta pre-pass, one kernel (a)
+//   VALU           no delta workspace, or head widths above 256
+struct BwdPlan { enum Kind { SPLIT_CROSS, SPLIT_DS_ONCE, SPLIT_PAIR, SPLIT_WIDE, MFMA, MFMA_WIDE, VALU } kind; int DT; bool zero_fill;
+                 Launch delta, a, b; int KS, VS; };
+BwdPlan plan_bwd(int dtype, bool have_ws, int B, int Tq, int Tk, int dh, int dvh, int H) {
+  const bool bf = dtype == TSG_BF16, split = have_ws && (bf || (dtype == TSG_F32S && k2_env().split));
+  const int DT = dh / 32, qblocks = cdiv(Tq, 128);
+  const Launch none{0, 0, 0}, delta{cdiv(B * Tq, 4), 256, 0};
+  if (split && split_widths_ok(dh, dvh, kSplitBwdMax)) {
+    const SplitLds& l = kSplitLds[DT];
+    if (Tk <= 32 && (!bf || qblocks == 1))                 // bf16 outputs cannot take the float atomics: several blocks go on below
+      return {BwdPlan::SPLIT_CROSS, DT, qblocks > 1, none, {B * H * qblocks, 256, l.cross}, none, 0, 0};
+    if (Tk <= 128 && Tk <= dh && !k2_env().pair)           // Q, K, V, dO are read once (self-attention over T <= 128 clips at head width 128)
+      return {BwdPlan::SPLIT_DS_ONCE, DT, false, delta, {B * H, 256, l.dkv}, {B * H * qblocks, 256, l.dq_from_ds}, 0, 0};
+    return {BwdPlan::SPLIT_PAIR, DT, false, none, {B * H * qblocks, 256, l.dq}, {B * H * cdiv(Tk, 128), 256, l.dkv}, 0, 0};
+  }
+  if (split && !bf && split_widths_ok(dh, dvh, kSplitBwdWideMax))
+    return {BwdPlan::SPLIT_WIDE, DT, false, none, {B * H * cdiv(Tq, 64), 256, kSplitLds[DT].wide}, {B * H * cdiv(Tk, 64), 256, kSplitLds[DT].wide}, 0, 0};
+  if (have_ws && dh <= DHMAX && dvh <= DHMAX) {
+    const int KS = roundup(dh, 64) + 2, VS2 = roundup(dvh, 64) + 2;
+    return {BwdPlan::MFMA, 0, false, delta, {B * H, kMfmaThreads, bwd_mfma_lds(KS, VS2)}, none, KS, VS2};
+  }
+  if (have_ws && dh <= DHW && dvh <= DHW)
+    return {BwdPlan::MFMA_WIDE, 0, false, delta, {B * H, kMfmaThreads, bwd_mfma_wide_lds(DHW + 2, DHW + 2)}, none, DHW + 2, DHW + 2};
+  return {BwdPlan::VALU, 0, false, none, {B * H, kThreads, 0}, none, 0, 0};
+}
+
+// allow: the (device, kernel)-keyed LDS attribute table, cheap when already set.  launch: one enqueue and its error check.
+template <typename K>
+int allow(const char* fn, K kern, size_t lds) {
+  const hipError_t e = allow_lds(kern, lds);
+  return e == hipSuccess ? 0 : set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
+}
+template <typename K, typename... Args>
+int launch(const K2Args& a, const Launch& k, K kern, Args... args) {
+  hipLaunchKernelGGL(kern, dim3(k.grid), dim3(k.threads), k.lds, a.st, args...);
+  return check_launch(a.fn);
+}
+
+template <int DT, typename ET>
+int launch_fwd_split(const FwdArgs& a, const FwdPlan& pl) {
+  auto kf = a.dc.thresh ? mha_fwd_split_kernel<DT, true, ET> : mha_fwd_split_kernel<DT, false, ET>;
+  if (int rc = allow(a.fn, kf, pl.k.lds)) return rc;
+  return launch(a, pl.k, kf, (const ET*)a.Q, (const ET*)a.K, (const ET*)a.V, (ET*)a.O, (float*)a.lse, a.B, a.Tq, a.Tk, a.dk, a.H, a.inv_scale,
+                a.causal, a.dc);
+}
+
+// exact fp32 MFMA kernels, regular and wide-head form
+int launch_fwd_mfma(const FwdArgs& a, const FwdPlan& pl) {
+  const bool drop = a.dc.thresh != 0, full = a.dk / a.H == DHMAX && a.dv / a.H == DHMAX;
+  auto kern = pl.kind == FwdPlan::MFMA_WIDE ? (drop ? mha_fwd_mfma_wide_kernel<true> : mha_fwd_mfma_wide_kernel<false>)
+              : drop ? (full ? mha_fwd_mfma_kernel<true, true> : mha_fwd_mfma_kernel<true, false>)
+                     : (full ? mha_fwd_mfma_kernel<false, true> : mha_fwd_mfma_kernel<false, false>);
+  if (pl.k.lds > 64 * 1024)
+    if (int rc = allow(a.fn, kern, pl.k.lds)) return rc;
+  return launch(a, pl.k, kern, (const float*)a.Q, (const float*)a.K, (const float*)a.V, (float*)a.O, (float*)a.lse, a.B, a.Tq, a.Tk, a.dk, a.dv,
+                a.H, a.inv_scale, a.causal, pl.qblocks, pl.KS, pl.VS, a.dc);
+}
+
+template <int DT, typename ET>
+int launch_bwd_cross(const BwdArgs& a, const BwdPlan& pl) {
+  auto kc = a.dc.thresh ? mha_bwd_split_cross_kernel<DT, true, ET> : mha_bwd_split_cross_kernel<DT, false, ET>;
+  if (int rc = allow(a.fn, kc, pl.a.lds)) return rc;
+  if (pl.zero_fill) {
+    const size_t nb = sizeof(float) * (size_t)a.B * a.Tk * a.dk;
+    hipError_t e = zero_async(a.dK, nb, a.st);
+    if (e == hipSuccess) e = zero_async(a.dV, nb, a.st);
+    if (e != hipSuccess) return set_error((int)e, "%s: zero fill: %s", a.fn, hipGetErrorString(e));
+  }
+  return launch(a, pl.a, kc, (const ET*)a.Q, (const ET*)a.K, (const ET*)a.V, (const ET*)a.dO, (const float*)a.lse, (const ET*)a.O, (ET*)a.dQ,
+                (ET*)a.dK, (ET*)a.dV, a.B, a.Tq, a.Tk, a.dk, a.H, a.inv_scale, a.causal, pl.zero_fill ? 1 : 0, a.dc);
+}
+
+template <int DT, typename ET>
+int launch_bwd_ds_once(const BwdArgs& a, const BwdPlan& pl) {
+  auto kw = a.dc.thresh ? mha_bwd_split_dkv_kernel<DT, true, ET, true> : mha_bwd_split_dkv_kernel<DT, false, ET, true>;
+  auto kx = mha_bwd_dq_from_ds_kernel<DT, ET>;
+  if (int rc = allow(a.fn, kw, pl.a.lds)) return rc;
+  if (int rc = allow(a.fn, kx, pl.b.lds)) return rc;
+  hipLaunchKernelGGL(mha_bwd_delta_t_kernel<ET>, dim3(pl.delta.grid), dim3(pl.delta.threads), 0, a.st, (const ET*)a.O, (const ET*)a.dO,
+                     (float*)a.delta, a.B, a.Tq, a.dk, a.H);
+  if (int rc = launch(a, pl.a, kw, (const ET*)a.Q, (const ET*)a.K, (const ET*)a.V, (const ET*)a.dO, (const float*)a.lse, (const float*)a.delta,
+                      (ET*)a.dK, (ET*)a.dV, (ET*)a.dQ, a.B, a.Tq, a.Tk, a.dk, a.H, a.inv_scale, a.causal, a.dc))
+    return rc;
+  return launch(a, pl.b, kx, (const ET*)a.K, (ET*)a.dQ, a.B, a.Tq, a.Tk, a.dk, a.H);
+}
+
+// SPLIT_PAIR and SPLIT_WIDE.  The dQ kernel runs first: it also writes delta = <dO, O>, which the dK/dV kernel reads (ds: the
+// regular dK/dV kernel's dS output, not written here; the wide one has no such argument)
+template <typename ET, typename KQ, typename KA, typename... DS>
+int launch_pair_kernels(const BwdArgs& a, const BwdPlan& pl, KQ kq, KA ka, DS... ds) {
+  if (int rc = allow(a.fn, ka, pl.b.lds)) return rc;
+  if (int rc = allow(a.fn, kq, pl.a.lds)) return rc;
+  if (int rc = launch(a, pl.a, kq, (const ET*)a.Q, (const ET*)a.K, (const ET*)a.V, (const ET*)a.dO, (const float*)a.lse, (const ET*)a.O,
+                      (float*)a.delta, (ET*)a.dQ, a.B, a.Tq, a.Tk, a.dk, a.H, a.inv_scale, a.causal, a.dc))
+    return rc;
+  return launch(a, pl.b, ka, (const ET*)a.Q, (const ET*)a.K, (const ET*)a.V, (const ET*)a.dO, (const float*)a.lse, (const float*)a.delta,
+                (ET*)a.dK, (ET*)a.dV, ds..., a.B, a.Tq, a.Tk, a.dk, a.H, a.inv_scale, a.causal, a.dc);
+}
+template <int DT, typename ET>
+int launch_bwd_pair(const BwdArgs& a, const BwdPlan& pl) {
+  return a.dc.thresh ? launch_pair_kernels<ET>(a, pl, mha_bwd_split_dq_kernel<DT, true, ET>, mha_bwd_split_dkv_kernel<DT, true, ET>, (ET*)nullptr)
+                     : launch_pair_kernels<ET>(a, pl, mha_bwd_split_dq_kernel<DT, false, ET>, mha_bwd_split_dkv_kernel<DT, false, ET>, (ET*)nullptr);
+}
+template <int DT>
+int launch_bwd_wide(const BwdArgs& a, const BwdPlan& pl) {
+  return a.dc.thresh ? launch_pair_kernels<float>(a, pl, mha_bwd_split_dq_wide_kernel<DT, true>, mha_bwd_split_dkv_wide_kernel<DT, true>)
+                     : launch_pair_kernels<float>(a, pl, mha_bwd_split_dq_wide_kernel<DT, false>, mha_bwd_split_dkv_wide_kernel<DT, false>);
+}
+
+// exact fp32 MFMA kernels, regular and wide-head form, after their delta pre-pass
+int launch_bwd_mfma(const BwdArgs& a, const BwdPlan& pl) {
+  if (int rc = launch(a, pl.delta, mha_bwd_delta_kernel, (const float*)a.O, (const float*)a.dO, (float*)a.delta, a.B, a.Tq, a.dv, a.H)) return rc;
+  const bool drop = a.dc.thresh != 0, full = a.dk / a.H == DHMAX && a.dv / a.H == DHMAX;
+  auto kern = pl.kind == BwdPlan::MFMA_WIDE ? (drop ? mha_bwd_mfma_wide_kernel<true> : mha_bwd_mfma_wide_kernel<false>)
+              : drop ? (full ? mha_bwd_mfma_kernel<true, true> : mha_bwd_mfma_kernel<true, false>)
+                     : (full ? mha_bwd_mfma_kernel<false, true> : mha_bwd_mfma_kernel<false, false>);
+  if (pl.a.lds > 64 * 1024)
+    if (int rc = allow(a.fn, kern, pl.a.lds)) return rc;
+  return launch(a, pl.a, kern, (const float*)a.Q, (const float*)a.K, (const float*)a.V, (const float*)a.dO, (const float*)a.lse,
+                (const float*)a.delta, (float*)a.dQ, (float*)a.dK, (float*)a.dV, a.B, a.Tq, a.Tk, a.dk, a.dv, a.H, a.inv_scale, a.causal,
+                pl.KS, pl.VS, a.dc);
+}
+
+// The storage type and DT = head width / 32 of the split kernels as template arguments
+template <typename ET>
+int launch_split(const FwdArgs& a, const FwdPlan& pl) {
+  if (pl.DT <= 4) TSG_DISPATCH_DT(pl.DT, 1, (launch_fwd_split<DT, ET>(a, pl)));
+  TSG_DISPATCH_DT(pl.DT, 5, (launch_fwd_split<DT, ET>(a, pl)));
+}
+template <typename ET>
+int launch_split(const BwdArgs& a, const BwdPlan& pl) {
+  switch (pl.kind) {
+    case BwdPlan::SPLIT_CROSS: TSG_DISPATCH_DT(pl.DT, 1, (launch_bwd_cross<DT, ET>(a, pl)));
+    case BwdPlan::SPLIT_DS_ONCE: TSG_DISPATCH_DT(pl.DT, 1, (launch_bwd_ds_once<DT, ET>(a, pl)));
+    default: TSG_DISPATCH_DT(pl.DT, 1, (launch_bwd_pair<DT, ET>(a, pl)));
+  }
+}
+
+// The argument checks every K2 entry point shares, after its pointers: dtype, dimensions, divisibility, head widths -- in this order
 int check(const char* fn, int B, int Tq, int Tk, int dk, int dv, int H, int dtype) {
   if (dtype != TSG_F32 && dtype != TSG_F32S && dtype != TSG_BF16)
     return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S or TSG_BF16)", fn, dtype);
@@ -2263,14 +2421,17 @@ int check(const char* fn, int B, int Tq, int Tk, int dk, int dv, int H, int dtyp
   return 0;
 }
 
-}  // namespace
-}  // namespace tsg
+int check_pointers(const char* fn, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) {
+    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
+    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
+  }
+  return 0;
+}
 
-using namespace tsg;
-
-static int make_drop(const char* fn, float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev, tsg::DropCfg* dc) {
+int make_drop(const char* fn, float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev, DropCfg* dc) {
   dc->rng = static_cast<const unsigned long long*>(rng_dev);
-  if (!(p_drop >= 0.f) || p_drop >= 1.f) return tsg::set_error(TSG_E_SHAPE, "%s: dropout probability %g outside [0, 1)", fn, p_drop);
+  if (!(p_drop >= 0.f) || p_drop >= 1.f) return set_error(TSG_E_SHAPE, "%s: dropout probability %g outside [0, 1)", fn, p_drop);
   const double t = (double)p_drop * 4294967296.0;
   dc->thresh = p_drop > 0.f ? (unsigned)(t < 1.0 ? 1.0 : (t > 4294967295.0 ? 4294967295.0 : t)) : 0u;
   dc->inv_keep = 1.f / (1.f - p_drop);
@@ -2279,107 +2440,71 @@ static int make_drop(const char* fn, float p_drop, uint64_t seed, uint64_t offse
   return 0;
 }
 
-static int mha_fwd_impl(const void* Q, const void* K, const void* V, void* O, void* A_sum, void* S_sum, void* lse,
-                        int B, int Tq, int Tk, int d_key, int d_value, int n_heads, float scale, int causal,
-                        float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev, int dtype, void* stream) {
+// order of the checks: NULL / alignment -> check -> dropout -> scale -> bf16 shape
+int mha_fwd_impl(const void* Q, const void* K, const void* V, void* O, void* A_sum, void* S_sum, void* lse,
+                 int B, int Tq, int Tk, int d_key, int d_value, int n_heads, float scale, int causal,
+                 float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev, int dtype, void* stream) {
   const char* fn = "tsg_mha_fwd";
-  for (const void* p : {Q, K, V, (const void*)O, (const void*)lse}) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  int rc = check(fn, B, Tq, Tk, d_key, d_value, n_heads, dtype);
-  if (rc) return rc;
-  DropCfg dc;
-  rc = make_drop(fn, p_drop, seed, offset, rng_dev, &dc);
-  if (rc) return rc;
+  FwdArgs a{{fn, B, Tq, Tk, d_key, d_value, n_heads, 0.f, causal, {}, static_cast<hipStream_t>(stream)}, Q, K, V, O, A_sum, S_sum, lse};
+  if (int rc = check_pointers(fn, {Q, K, V, O, lse})) return rc;
+  if (int rc = check(fn, B, Tq, Tk, d_key, d_value, n_heads, dtype)) return rc;
+  if (int rc = make_drop(fn, p_drop, seed, offset, rng_dev, &a.dc)) return rc;
   if (!(scale > 0.f)) return set_error(TSG_E_SHAPE, "%s: scale must be positive", fn);
-  if (dtype == TSG_BF16 && (A_sum || S_sum || d_key != d_value || (d_key / n_heads) % 32 || d_key / n_heads > 256))     // before any launch
-    return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs d_key == d_value, head widths 32 .. 256 in steps of 32 and no A_sum / S_sum "
-                     "outputs (head width %d / %d)", fn, d_key / n_heads, d_value / n_heads);
-  auto st = static_cast<hipStream_t>(stream);
-  const size_t map_bytes = sizeof(float) * (size_t)B * Tq * Tk;
-  if (A_sum) { hipError_t e = zero_async(A_sum, map_bytes, st); if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e)); }
-  if (S_sum) { hipError_t e = zero_async(S_sum, map_bytes, st); if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e)); }
+  a.inv_scale = 1.f / scale;
   const int dh = d_key / n_heads, dvh = d_value / n_heads;
-  static int split_on = -1;                                         // TSG_MHA_SPLIT=0: exact-fp32 kernels also for TSG_F32S (A/B)
-  if (split_on < 0) { const char* e = getenv("TSG_MHA_SPLIT"); split_on = e ? atoi(e) : 1; }
-  if (dtype == TSG_BF16) {                       // bf16 storage of Q, K, V, O: the split kernels with 2-byte elements (lo planes zero)
-    if (A_sum || S_sum || dh != dvh || dh % 32 || dh > 256)
-      return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs d_key == d_value, head widths 32 .. 256 in steps of 32 and no A_sum / S_sum "
-                       "outputs (head width %d / %d)", fn, dh, dvh);
-    const bf16_t* q = (const bf16_t*)Q; const bf16_t* k = (const bf16_t*)K; const bf16_t* v = (const bf16_t*)V;
-    const float is = 1.f / scale;
-#define TSG_SPLIT_CASE(DT) \
-    return dc.thresh ? launch_fwd_split<DT, true, bf16_t>(fn, q, k, v, (bf16_t*)O, (float*)lse, B, Tq, Tk, d_key, n_heads, is, causal, dc, st) \
-                     : launch_fwd_split<DT, false, bf16_t>(fn, q, k, v, (bf16_t*)O, (float*)lse, B, Tq, Tk, d_key, n_heads, is, causal, dc, st)
-    switch (dh / 32) {
-      case 1: TSG_SPLIT_CASE(1);
-      case 2: TSG_SPLIT_CASE(2);
-      case 3: TSG_SPLIT_CASE(3);
-      case 4: TSG_SPLIT_CASE(4);
-      case 5: TSG_SPLIT_CASE(5);
-      case 6: TSG_SPLIT_CASE(6);
-      case 7: TSG_SPLIT_CASE(7);
-      default: TSG_SPLIT_CASE(8);
+  const bool maps = A_sum || S_sum;
+  if (dtype == TSG_BF16 && (maps || !split_widths_ok(dh, dvh, kSplitFwdMax)))                       // before any launch
+    return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs d_key == d_value, head widths 32 .. 256 in steps of 32 and no A_sum / S_sum "
+                     "outputs (head width %d / %d)", fn, dh, dvh);
+  for (void* m : {A_sum, S_sum})
+    if (m) {
+      const hipError_t e = zero_async(m, sizeof(float) * (size_t)B * Tq * Tk, a.st);
+      if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
     }
-#undef TSG_SPLIT_CASE
+  const FwdPlan pl = plan_fwd(dtype, maps, B, Tq, dh, dvh, n_heads);
+  switch (pl.kind) {
+    case FwdPlan::SPLIT: return dtype == TSG_BF16 ? launch_split<bf16_t>(a, pl) : launch_split<float>(a, pl);
+    case FwdPlan::MFMA:
+    case FwdPlan::MFMA_WIDE: return launch_fwd_mfma(a, pl);
+    case FwdPlan::VALU: break;
   }
-  if (dtype == TSG_F32S && split_on && !A_sum && !S_sum && dh == dvh && dh % 32 == 0 && dh <= 256) {     // split precision
-    const float* q = (const float*)Q; const float* k = (const float*)K; const float* v = (const float*)V;
-    const float is = 1.f / scale;
-#define TSG_SPLIT_CASE(DT) \
-    return dc.thresh ? launch_fwd_split<DT, true>(fn, q, k, v, (float*)O, (float*)lse, B, Tq, Tk, d_key, n_heads, is, causal, dc, st) \
-                     : launch_fwd_split<DT, false>(fn, q, k, v, (float*)O, (float*)lse, B, Tq, Tk, d_key, n_heads, is, causal, dc, st)
-    switch (dh / 32) {
-      case 1: TSG_SPLIT_CASE(1);
-      case 2: TSG_SPLIT_CASE(2);
-      case 3: TSG_SPLIT_CASE(3);
-      case 4: TSG_SPLIT_CASE(4);
-      case 5: TSG_SPLIT_CASE(5);
-      case 6: TSG_SPLIT_CASE(6);
-      case 7: TSG_SPLIT_CASE(7);
-      default: TSG_SPLIT_CASE(8);
-    }
-#undef TSG_SPLIT_CASE
-  }
-  if (!A_sum && !S_sum && dh <= DHMAX && dvh <= DHMAX) {            // MFMA path
-    const int KS = roundup(dh, 64) + 2, VS = roundup(dvh, 32) + 4, qblocks = cdiv(Tq, QB);
-    size_t lds = sizeof(float) * (size_t)32 * (KS + VS);
-    const size_t qstage = sizeof(float) * (size_t)QB * KS, ostage = sizeof(float) * (size_t)QB * VS;
-    if (qstage > lds) lds = qstage;
-    if (ostage > lds) lds = ostage;
-    const bool full = dh == DHMAX && dvh == DHMAX;
-    auto kern = dc.thresh ? (full ? mha_fwd_mfma_kernel<true, true> : mha_fwd_mfma_kernel<true, false>)
-                          : (full ? mha_fwd_mfma_kernel<false, true> : mha_fwd_mfma_kernel<false, false>);
-    if (lds > 64 * 1024) {
-      hipError_t e = allow_lds(kern, lds);
-      if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(B * qblocks * n_heads), dim3(kMfmaThreads), lds, st, (const float*)Q, (const float*)K,
-                       (const float*)V, (float*)O, (float*)lse, B, Tq, Tk, d_key, d_value, n_heads, 1.f / scale, causal,
-                       qblocks, KS, VS, dc);
-    return check_launch(fn);
-  }
-  if (!A_sum && !S_sum && dh <= DHW && dvh <= DHW) {                // MFMA path for wide heads (channels split over the waves)
-    const int KS = DHW + 2, VS = DHW + 4, qblocks = cdiv(Tq, QBW);
-    size_t lds = sizeof(float) * ((size_t)32 * (KS + VS) + 2 * 4 * 16 * 64);
-    const size_t qstage = sizeof(float) * (size_t)QBW * KS, ostage = sizeof(float) * (size_t)QBW * VS;
-    if (qstage > lds) lds = qstage;
-    if (ostage > lds) lds = ostage;
-    auto kern = dc.thresh ? mha_fwd_mfma_wide_kernel<true> : mha_fwd_mfma_wide_kernel<false>;
-    hipError_t e = allow_lds(kern, lds);
-    if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(B * qblocks * n_heads), dim3(kWideThreads), lds, st, (const float*)Q, (const float*)K,
-                       (const float*)V, (float*)O, (float*)lse, B, Tq, Tk, d_key, d_value, n_heads, 1.f / scale, causal,
-                       qblocks, KS, VS, dc);
-    return check_launch(fn);
-  }
-  const int qtiles = cdiv(Tq, TQ);
-  hipLaunchKernelGGL(mha_fwd_kernel, dim3(B * qtiles), dim3(kThreads), 0, st, (const float*)Q, (const float*)K,
-                     (const float*)V, (float*)O, (float*)A_sum, (float*)S_sum, (float*)lse, B, Tq, Tk, d_key, d_value,
-                     n_heads, 1.f / scale, causal, qtiles, dc);
-  return check_launch(fn);
+  return launch(a, pl.k, mha_fwd_kernel, (const float*)Q, (const float*)K, (const float*)V, (float*)O, (float*)A_sum, (float*)S_sum, (float*)lse,
+                B, Tq, Tk, d_key, d_value, n_heads, a.inv_scale, causal, pl.qblocks, a.dc);
 }
+
+// order of the checks: NULL / alignment -> check -> dropout -> bf16 shape (no scale check here)
+int mha_bwd_impl(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* lse,
+                 void* dQ, void* dK, void* dV, void* delta_ws, int B, int Tq, int Tk, int d_key, int d_value,
+                 int n_heads, float scale, int causal, float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev,
+                 int dtype, void* stream) {
+  const char* fn = "tsg_mha_bwd";
+  BwdArgs a{{fn, B, Tq, Tk, d_key, d_value, n_heads, 1.f / scale, causal, {}, static_cast<hipStream_t>(stream)},
+            Q, K, V, O, dO, lse, dQ, dK, dV, delta_ws};
+  if (int rc = check_pointers(fn, {Q, K, V, O, dO, lse, dQ, dK, dV})) return rc;
+  if (int rc = check(fn, B, Tq, Tk, d_key, d_value, n_heads, dtype)) return rc;
+  if (int rc = make_drop(fn, p_drop, seed, offset, rng_dev, &a.dc)) return rc;
+  const int dh = d_key / n_heads, dvh = d_value / n_heads;
+  if (dtype == TSG_BF16 && (!delta_ws || !split_widths_ok(dh, dvh, kSplitBwdMax)))
+    return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs delta_ws, d_key == d_value and head widths 32 .. 128 in steps of 32 "
+                     "(head width %d / %d)", fn, dh, dvh);
+  const BwdPlan pl = plan_bwd(dtype, delta_ws != nullptr, B, Tq, Tk, dh, dvh, n_heads);
+  switch (pl.kind) {
+    case BwdPlan::SPLIT_CROSS:
+    case BwdPlan::SPLIT_DS_ONCE:
+    case BwdPlan::SPLIT_PAIR: return dtype == TSG_BF16 ? launch_split<bf16_t>(a, pl) : launch_split<float>(a, pl);
+    case BwdPlan::SPLIT_WIDE: TSG_DISPATCH_DT(pl.DT, 5, (launch_bwd_wide<DT>(a, pl)));
+    case BwdPlan::MFMA:
+    case BwdPlan::MFMA_WIDE: return launch_bwd_mfma(a, pl);
+    case BwdPlan::VALU: break;
+  }
+  return launch(a, pl.a, mha_bwd_kernel, (const float*)Q, (const float*)K, (const float*)V, (const float*)O, (const float*)dO, (const float*)lse,
+                (float*)dQ, (float*)dK, (float*)dV, B, Tq, Tk, d_key, d_value, n_heads, a.inv_scale, causal, a.dc);
+}
+
+}  // namespace
+}  // namespace tsg
+
+using namespace tsg;
 
 extern "C" int tsg_mha_fwd(const void* Q, const void* K, const void* V, void* O, void* A_sum, void* S_sum, void* lse,
                            int B, int Tq, int Tk, int d_key, int d_value, int n_heads, float scale, int causal,
@@ -2391,121 +2516,6 @@ extern "C" int tsg_mha_fwd_rng(const void* Q, const void* K, const void* V, void
                                float p_drop, const void* rng_dev, int dtype, void* stream) {
   if (p_drop > 0.f && !rng_dev) return set_error(TSG_E_NULL, "tsg_mha_fwd_rng: rng_dev is NULL");
   return mha_fwd_impl(Q, K, V, O, A_sum, S_sum, lse, B, Tq, Tk, d_key, d_value, n_heads, scale, causal, p_drop, 0, 0, rng_dev, dtype, stream);
-}
-
-static int mha_bwd_impl(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* lse,
-                        void* dQ, void* dK, void* dV, void* delta_ws, int B, int Tq, int Tk, int d_key, int d_value,
-                        int n_heads, float scale, int causal, float p_drop, uint64_t seed, uint64_t offset, const void* rng_dev,
-                        int dtype, void* stream) {
-  const char* fn = "tsg_mha_bwd";
-  for (const void* p : {Q, K, V, O, dO, lse, (const void*)dQ, (const void*)dK, (const void*)dV}) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  int rc = check(fn, B, Tq, Tk, d_key, d_value, n_heads, dtype);
-  if (rc) return rc;
-  DropCfg dc;
-  rc = make_drop(fn, p_drop, seed, offset, rng_dev, &dc);
-  if (rc) return rc;
-  const int dh = d_key / n_heads, dvh = d_value / n_heads;
-  static int split_on = -1;                                         // TSG_MHA_SPLIT=0: exact-fp32 kernels also for TSG_F32S (A/B)
-  if (split_on < 0) { const char* e = getenv("TSG_MHA_SPLIT"); split_on = e ? atoi(e) : 1; }
-  if (dtype == TSG_BF16) {                       // bf16 storage of Q, K, V, O, dO, dQ, dK, dV (head widths up to 128)
-    if (!delta_ws || dh != dvh || dh % 32 || dh > 128)
-      return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs delta_ws, d_key == d_value and head widths 32 .. 128 in steps of 32 "
-                       "(head width %d / %d)", fn, dh, dvh);
-    auto st = static_cast<hipStream_t>(stream);
-    typedef bf16_t E;
-    const float is = 1.f / scale;
-#define TSG_SPLIT_CASE(DT) \
-    return dc.thresh ? launch_bwd_split<DT, true, E>(fn, (const E*)Q, (const E*)K, (const E*)V, (const E*)O, (const E*)dO, (const float*)lse, (float*)delta_ws, \
-                                                     (E*)dQ, (E*)dK, (E*)dV, B, Tq, Tk, d_key, n_heads, is, causal, dc, st) \
-                     : launch_bwd_split<DT, false, E>(fn, (const E*)Q, (const E*)K, (const E*)V, (const E*)O, (const E*)dO, (const float*)lse, (float*)delta_ws, \
-                                                      (E*)dQ, (E*)dK, (E*)dV, B, Tq, Tk, d_key, n_heads, is, causal, dc, st)
-    switch (dh / 32) {
-      case 1: TSG_SPLIT_CASE(1);
-      case 2: TSG_SPLIT_CASE(2);
-      case 3: TSG_SPLIT_CASE(3);
-      default: TSG_SPLIT_CASE(4);
-    }
-#undef TSG_SPLIT_CASE
-  }
-  // split-precision path (one key tile: the fused kernel, else the dK/dV + dQ pair)
-  if (dtype == TSG_F32S && split_on && delta_ws && dh == dvh && dh % 32 == 0 && dh <= 128) {
-    auto st = static_cast<hipStream_t>(stream);
-    const float* q = (const float*)Q; const float* k = (const float*)K; const float* v = (const float*)V; const float* g = (const float*)dO;
-    const float* o = (const float*)O; const float* l = (const float*)lse; float* dl = (float*)delta_ws;
-    float* dq = (float*)dQ; float* dk_ = (float*)dK; float* dv_ = (float*)dV;
-    const float is = 1.f / scale;
-#define TSG_SPLIT_CASE(DT) \
-    return dc.thresh ? launch_bwd_split<DT, true>(fn, q, k, v, o, g, l, dl, dq, dk_, dv_, B, Tq, Tk, d_key, n_heads, is, causal, dc, st) \
-                     : launch_bwd_split<DT, false>(fn, q, k, v, o, g, l, dl, dq, dk_, dv_, B, Tq, Tk, d_key, n_heads, is, causal, dc, st)
-    switch (dh / 32) {
-      case 1: TSG_SPLIT_CASE(1);
-      case 2: TSG_SPLIT_CASE(2);
-      case 3: TSG_SPLIT_CASE(3);
-      default: TSG_SPLIT_CASE(4);
-    }
-#undef TSG_SPLIT_CASE
-  }
-  if (dtype == TSG_F32S && split_on && delta_ws && dh == dvh && dh % 32 == 0 && dh > 128 && dh <= 256) {    // wide heads: channel halves per wave pair
-    auto st = static_cast<hipStream_t>(stream);
-    const float* q = (const float*)Q; const float* k = (const float*)K; const float* v = (const float*)V; const float* g = (const float*)dO;
-    const float* o = (const float*)O; const float* l = (const float*)lse; float* dl = (float*)delta_ws;
-    float* dq = (float*)dQ; float* dk_ = (float*)dK; float* dv_ = (float*)dV;
-    const float is = 1.f / scale;
-#define TSG_SPLIT_CASE(DT) \
-    return dc.thresh ? launch_bwd_split_wide<DT, true>(fn, q, k, v, o, g, l, dl, dq, dk_, dv_, B, Tq, Tk, d_key, n_heads, is, causal, dc, st) \
-                     : launch_bwd_split_wide<DT, false>(fn, q, k, v, o, g, l, dl, dq, dk_, dv_, B, Tq, Tk, d_key, n_heads, is, causal, dc, st)
-    switch (dh / 32) {
-      case 5: TSG_SPLIT_CASE(5);
-      case 6: TSG_SPLIT_CASE(6);
-      case 7: TSG_SPLIT_CASE(7);
-      default: TSG_SPLIT_CASE(8);
-    }
-#undef TSG_SPLIT_CASE
-  }
-  if (delta_ws && dh <= DHMAX && dvh <= DHMAX) {                    // MFMA path
-    auto st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(mha_bwd_delta_kernel, dim3(cdiv(B * Tq, 4)), dim3(256), 0, st, (const float*)O, (const float*)dO,
-                       (float*)delta_ws, B, Tq, d_value, n_heads);
-    rc = check_launch(fn);
-    if (rc) return rc;
-    const int KS = roundup(dh, 64) + 2, VS2 = roundup(dvh, 64) + 2;
-    const size_t lds = sizeof(float) * ((size_t)64 * (KS + VS2) + 2 * 4 * 16 * 64 + 32 * 66 + 64);
-    const bool full = dh == DHMAX && dvh == DHMAX;
-    auto kern = dc.thresh ? (full ? mha_bwd_mfma_kernel<true, true> : mha_bwd_mfma_kernel<true, false>)
-                          : (full ? mha_bwd_mfma_kernel<false, true> : mha_bwd_mfma_kernel<false, false>);
-    if (lds > 64 * 1024) {
-      hipError_t e = allow_lds(kern, lds);
-      if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(B * n_heads), dim3(kMfmaThreads), lds, st, (const float*)Q, (const float*)K, (const float*)V,
-                       (const float*)dO, (const float*)lse, (const float*)delta_ws, (float*)dQ, (float*)dK, (float*)dV,
-                       B, Tq, Tk, d_key, d_value, n_heads, 1.f / scale, causal, KS, VS2, dc);
-    return check_launch(fn);
-  }
-  if (delta_ws && dh <= DHW && dvh <= DHW) {                        // MFMA path for wide heads
-    auto st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(mha_bwd_delta_kernel, dim3(cdiv(B * Tq, 4)), dim3(256), 0, st, (const float*)O, (const float*)dO,
-                       (float*)delta_ws, B, Tq, d_value, n_heads);
-    rc = check_launch(fn);
-    if (rc) return rc;
-    const int KS = DHW + 2, VS2 = DHW + 2;
-    const size_t lds = sizeof(float) * ((size_t)32 * (2 * KS + VS2) + 2 * 4 * 16 * 64 + 32 * 66 + 64);
-    auto kern = dc.thresh ? mha_bwd_mfma_wide_kernel<true> : mha_bwd_mfma_wide_kernel<false>;
-    hipError_t e = allow_lds(kern, lds);
-    if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    hipLaunchKernelGGL(kern, dim3(B * n_heads), dim3(kMfmaThreads), lds, st, (const float*)Q, (const float*)K, (const float*)V,
-                       (const float*)dO, (const float*)lse, (const float*)delta_ws, (float*)dQ, (float*)dK, (float*)dV,
-                       B, Tq, Tk, d_key, d_value, n_heads, 1.f / scale, causal, KS, VS2, dc);
-    return check_launch(fn);
-  }
-  hipLaunchKernelGGL(mha_bwd_kernel, dim3(B * n_heads), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                     (const float*)Q, (const float*)K, (const float*)V, (const float*)O, (const float*)dO,
-                     (const float*)lse, (float*)dQ, (float*)dK, (float*)dV, B, Tq, Tk, d_key, d_value, n_heads,
-                     1.f / scale, causal, dc);
-  return check_launch(fn);
 }
 
 extern "C" int tsg_mha_bwd(const void* Q, const void* K, const void* V, const void* O, const void* dO, const void* lse,

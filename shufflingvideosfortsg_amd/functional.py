@@ -992,7 +992,8 @@ class _MHA(torch.autograd.Function):
 
 def mha_bf16_ok(d_key: int, d_value: int, n_heads: int, want_maps: bool = False) -> bool:
     """Shapes tsg_mha_fwd AND tsg_mha_bwd take with dtype TSG_BF16 (include/tsg_hip.h): equal key / value widths, head widths
-    32 .. 128 in steps of 32, no A_forward maps."""
+    32 .. 128 in steps of 32, no A_forward maps.  The limits are those of split_widths_ok(dh, dvh, kSplitBwdMax) in csrc/mha.hip,
+    the one predicate the host's plans use (the backward's limit: the forward alone takes widths up to kSplitFwdMax = 256)."""
     dh = d_key // max(n_heads, 1)
     return (not want_maps) and d_key == d_value and d_key % max(n_heads, 1) == 0 and dh % 32 == 0 and 32 <= dh <= 128
 
@@ -1021,12 +1022,14 @@ def mha(Q, K, V, n_heads, scale, causal=False, return_maps=False, p_drop=0.0):
             rng = st.clone()                                        # this call's (seed, offset), shared by forward and backward
         else:
             offset = int(torch.randint(0, 2 ** 62, (1,)).item())
-    if Q.dtype == _BF and not mha_bf16_ok(Q.shape[-1], V.shape[-1], n_heads, return_maps):
-        # bf16 storage mode, a shape the TSG_BF16 kernels do not take (A_forward maps, head widths that are not multiples of 32 or
-        # above 128, d_key != d_value): the fp32-storage kernels on fp32 copies, O rounded back
-        O, A, S = _MHA.apply(Q.float(), K.float(), V.float(), n_heads, scale, causal, return_maps, float(p_drop), seed, offset, rng)
-        return (O.to(_BF), A, S) if return_maps else O.to(_BF)
+    # bf16 storage mode, a shape the TSG_BF16 kernels do not take (A_forward maps, head widths that are not multiples of 32 or
+    # above 128, d_key != d_value): the fp32-storage kernels on fp32 copies, O rounded back
+    copies = Q.dtype == _BF and not mha_bf16_ok(Q.shape[-1], V.shape[-1], n_heads, return_maps)
+    if copies:
+        Q, K, V = Q.float(), K.float(), V.float()
     O, A, S = _MHA.apply(Q, K, V, n_heads, scale, causal, return_maps, float(p_drop), seed, offset, rng)
+    if copies:
+        O = O.to(_BF)
     return (O, A, S) if return_maps else O
 
 

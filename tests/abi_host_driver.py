@@ -72,6 +72,32 @@ def run_checks(lib):
     eq(lib.tsg_mha_fwd(p, p, p, p, p, None, p, 1, 4, 4, 64, 64, 2, 1.0, 0, 0.0, 0, 0, TSG_BF16, None), -2, "A_sum in bf16")
     eq(lib.tsg_mha_fwd(p, p, p, p, None, None, p, 1, 4, 4, 40, 40, 2, 1.0, 0, 0.0, 0, 0, TSG_BF16, None), -2, "head width 20")
     eq(lib.tsg_mha_bwd(p, p, p, p, p, p, p, p, p, p, 1, 4, 4, 512, 512, 2, 1.0, 0, 0.0, 0, 0, TSG_BF16, None), -2, "head width 256")
+    # K2 calls that are wrong in several ways at once: the code and the text of the FIRST failing check, in the order NULL / alignment ->
+    # dtype -> dimensions -> divisibility -> head widths -> dropout -> scale (forward only) -> bf16 shape
+    def k2(rc, want, text, what):
+        eq(rc, want, what)
+        assert text in lib.tsg_last_error(), f"{what}: {lib.tsg_last_error()}"
+
+    def fwd(Q=p, A=None, B=1, dk=8, dv=8, H=2, scale=1.0, pd=0.0, dt=TSG_F32):
+        return lib.tsg_mha_fwd(Q, p, p, p, A, None, p, B, 4, 4, dk, dv, H, scale, 0, pd, 0, 0, dt, None)
+
+    def bwd(ws=p, dk=64, H=2, dt=TSG_BF16):
+        return lib.tsg_mha_bwd(p, p, p, p, p, p, p, p, p, ws, 1, 4, 4, dk, dk, H, 1.0, 0, 0.0, 0, 0, dt, None)
+    k2(fwd(Q=None, dt=7), -1, b"tsg_mha_fwd: NULL pointer argument", "NULL Q and dtype 7")
+    k2(fwd(Q=p + 4, B=0), -3, b"is not 16-byte aligned", "misaligned Q and B = 0")
+    k2(fwd(B=0, dt=7), -4, b"tsg_mha_fwd: dtype 7 not supported", "dtype 7 and B = 0")
+    k2(fwd(H=3, pd=1.0), -2, b"d_key=8 / d_value=8 not divisible by n_heads=3", "8 % 3 and p_drop = 1")
+    k2(fwd(pd=1.0, scale=0.0), -2, b"dropout probability 1 outside [0, 1)", "p_drop = 1 and scale = 0")
+    k2(fwd(A=p, dk=64, dv=64, scale=0.0, dt=TSG_BF16), -2, b"tsg_mha_fwd: scale must be positive", "scale = 0, bf16 and A_sum")
+    k2(fwd(dk=12, dv=12), -3, b"head widths 6 / 6 must be multiples of 4", "head width 6")
+    k2(fwd(dv=1032), -2, b"value head width 516 > 512 not supported", "value head width 516")
+    k2(bwd(ws=None), -2, b"tsg_mha_bwd: dtype TSG_BF16 needs delta_ws, d_key == d_value and head widths 32 .. 128 in steps of 32 "
+       b"(head width 32 / 32)", "bf16 backward without delta_ws")
+    k2(bwd(dk=320), -2, b"in steps of 32 (head width 160 / 160)", "bf16 backward at head width 160")
+    k2(lib.tsg_mha_fwd_rng(None, p, p, p, None, None, p, 1, 4, 4, 8, 8, 2, 1.0, 0, 0.5, None, TSG_F32, None), -1,
+       b"tsg_mha_fwd_rng: rng_dev is NULL", "fwd_rng: p_drop > 0, no rng_dev, NULL Q")
+    k2(lib.tsg_mha_bwd_rng(None, p, p, p, p, p, p, p, p, p, 1, 4, 4, 8, 8, 2, 1.0, 0, 0.5, None, TSG_F32, None), -1,
+       b"tsg_mha_bwd_rng: rng_dev is NULL", "bwd_rng: p_drop > 0, no rng_dev, NULL Q")
     eq(lib.tsg_lstm_fwd_bias(p, None, p, p, p, p, p, 4, 16, 100, TSG_BF16, 1, None), -2, "h = 100")
     eq(lib.tsg_lstm_fwd_bias(p, None, p, p, p, p, None, 4, 16, 128, TSG_BF16, 1, None), -2, "no sync workspace")
     eq(lib.tsg_lstm_bwd_ws_layout(p, p, p, p, None, p, p, None, 0, None, 4, 16, 128, TSG_BF16, 1, None), -2, "no ring workspace")

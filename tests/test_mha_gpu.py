@@ -280,3 +280,197 @@ def test_split_precision_attention_in_a_captured_graph():
         assert torch.equal(o0, o_e) and not torch.equal(o1, a)   # the captured offset increment gives every replay a new mask
     finally:
         F.set_gemm_dtype(None)
+
+
+# ---- which kernel a shape gets: the smallest shapes on either side of every boundary of the host's plan ----
+
+def _ref64(Q, K, V, gO, h, scale, mask=None, p=0.0):
+    """float64 autograd of the formula (optionally with a given keep mask [B, h, Tq, Tk]): O, (dQ, dK, dV), A_sum, S_sum"""
+    q, k, v = (t.double().requires_grad_(True) for t in (Q, K, V))
+    B, Tq, d = Q.shape
+    Tk, dv = V.shape[1:]
+    qh, kh = (t.view(B, -1, h, d // h).transpose(1, 2) for t in (q, k))
+    A = qh @ kh.transpose(-1, -2) / scale
+    S = torch.softmax(A, -1)
+    P = S if mask is None else S * mask.double() / (1 - p)
+    o = (P @ v.view(B, Tk, h, dv // h).transpose(1, 2)).transpose(1, 2).reshape(B, Tq, dv)
+    o.backward(gO.double())
+    return o.detach(), [t.grad for t in (q, k, v)], A.detach().sum(1), S.detach().sum(1)
+
+
+def _drop_mask(B, h, Tq, Tk, p):
+    """The keep mask F.mha draws right after torch.manual_seed(5): a function of (seed, offset, b, head, q, key) only, read off the
+    exact kernel with one identity block per head as V (as test_attention_dropout_mask_forward_backward does)."""
+    from shufflingvideosfortsg_amd import functional as F
+    torch.manual_seed(5)
+    seed, offset = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF, int(torch.randint(0, 2 ** 62, (1,)).item())
+    Tp = (Tk + 3) // 4 * 4
+    Vi = torch.zeros(B, Tk, h, Tp, device="cuda")
+    Vi[:, :, :, :Tk] = torch.eye(Tk, device="cuda")[None, :, None, :]
+    Q = torch.zeros(B, Tq, 4 * h, device="cuda"); K = torch.zeros(B, Tk, 4 * h, device="cuda")       # uniform softmax: no entry underflows
+    Sd = F._MHA.apply(Q, K, Vi.view(B, Tk, h * Tp), h, 1.0, False, False, p, seed, offset)[0]
+    return (Sd.view(B, Tq, h, Tp)[..., :Tk] != 0).transpose(1, 2)
+
+
+def _edge_inputs(B, Tq, Tk, d, dv, bf):
+    g = torch.Generator().manual_seed(Tq + Tk)
+    ts = [torch.randn(B, n, w, generator=g) for n, w in ((Tq, d), (Tk, d), (Tk, dv), (Tq, dv))]
+    return [(t.to(torch.bfloat16).float() if bf else t).cuda() for t in ts]
+
+
+def _edge_run(mode, Q, K, V, gO, h, p=0.0):
+    """forward + backward through functional.mha in "f32s" (split precision), "fp32" (strict) or "bf16" (storage) mode"""
+    from shufflingvideosfortsg_amd import functional as F
+    cast = (lambda t: t.to(torch.bfloat16)) if mode == "bf16" else (lambda t: t.clone())
+    F.set_gemm_dtype("f32s" if mode == "f32s" else None)
+    try:
+        q, k, v = (cast(t).requires_grad_(True) for t in (Q, K, V))
+        torch.manual_seed(5)                                     # the same dropout (seed, offset) in every run
+        o = F.mha(q, k, v, h, math.sqrt(Q.shape[-1]), False, p_drop=p)
+        o.backward(cast(gO))
+        return o.detach(), [t.grad for t in (q, k, v)]
+    finally:
+        F.set_gemm_dtype(None)
+
+
+def _edge_check(mode, d, dv, h, Tq, Tk, p=0.0, B=1):
+    from test_bf16_storage_gpu import _close
+    Q, K, V, gO = _edge_inputs(B, Tq, Tk, d, dv, mode == "bf16")
+    o, gr = _edge_run(mode, Q, K, V, gO, h, p)
+    o2, gr2 = _edge_run(mode, Q, K, V, gO, h, p)
+    assert torch.equal(o, o2) and torch.equal(gr[0], gr2[0])     # one writer (or an ordered fold) per output element, except dK / dV
+    if not (mode == "f32s" and Tk <= 32 and Tq > 128):           # of the one-tile kernel with several query blocks (float atomics)
+        assert torch.equal(gr[1], gr2[1]) and torch.equal(gr[2], gr2[2])
+    split = mode == "f32s" and d == dv and (d // h) % 32 == 0 and d // h <= 256
+    if p > 0.0 and split:                                        # the exact kernels under the same (seed, offset)
+        o_e, g_e = _edge_run("fp32", Q, K, V, gO, h, p)
+        torch.testing.assert_close(o, o_e, atol=2e-5 * float(o_e.abs().max()), rtol=1e-4)
+        for a, b_, name in zip(gr, g_e, "QKV"):
+            torch.testing.assert_close(a, b_, atol=2e-5 * float(b_.abs().max()) + 1e-7, rtol=1e-4, msg=lambda m, n=name: f"d{n}: {m}")
+        return
+    mask = _drop_mask(B, h, Tq, Tk, p) if p > 0.0 else None
+    o64, g64, _, _ = _ref64(Q, K, V, gO, h, math.sqrt(d), mask, p)
+    if mode == "bf16":
+        for got, want, name in zip([o] + gr, [o64] + g64, ("O", "dQ", "dK", "dV")):
+            assert got.dtype == torch.bfloat16
+            _close(got, want.float().cpu(), name)
+    elif p > 0.0:                                                # exact kernels with dropout: the dropout test's bounds
+        torch.testing.assert_close(o.double(), o64, atol=1e-4, rtol=1e-4)
+        for a, t, name in zip(gr, g64, "QKV"):
+            torch.testing.assert_close(a.double(), t, atol=2e-4, rtol=2e-3, msg=lambda m, n=name: f"d{n}: {m}")
+    elif mode == "f32s":
+        assert float((o.double() - o64).abs().max()) < 2e-5 * float(o64.abs().max())
+        for a, t, name in zip(gr, g64, "QKV"):
+            assert float((a.double() - t).abs().max()) < 2e-5 * float(t.abs().max()) + 1e-7, name
+    else:
+        torch.testing.assert_close(o.double(), o64, **TOL)
+        for a, t, name in zip(gr, g64, "QKV"):
+            torch.testing.assert_close(a.double(), t, atol=2e-4, rtol=1e-3, msg=lambda m, n=name: f"d{n}: {m}")
+
+
+def _edge_maps():
+    """return_maps=True: the VALU forward with the A_forward side outputs, in strict fp32."""
+    from shufflingvideosfortsg_amd import functional as F
+    Q, K, V, gO = _edge_inputs(1, 9, 5, 32, 32, False)
+    o, A, S = F.mha(Q, K, V, 4, math.sqrt(32), False, return_maps=True)
+    o2, A2, S2 = F.mha(Q, K, V, 4, math.sqrt(32), False, return_maps=True)
+    assert torch.equal(o, o2)
+    o64, _, A64, S64 = _ref64(Q, K, V, gO, 4, math.sqrt(32))
+    torch.testing.assert_close(o.double(), o64, **TOL)
+    torch.testing.assert_close(S.double(), S64, **TOL)
+    torch.testing.assert_close(A.double(), A64, atol=1e-3, rtol=1e-5)
+
+
+def _edge_bf16_lib(d):
+    """bf16 storage at head widths 160 / 256 (split forward DT 5 / 8): tsg_mha_fwd takes them, tsg_mha_bwd does not, so mha() sends
+    those widths to fp32 copies -- forward only, through the library."""
+    from shufflingvideosfortsg_amd import _lib
+    from shufflingvideosfortsg_amd._lib import ptr, TSG_BF16
+    from test_bf16_storage_gpu import _close
+    lib = _lib.load(); st = torch.cuda.current_stream().cuda_stream
+    B, Tq, Tk, h = 1, 40, 20, 2
+    Q, K, V, gO = _edge_inputs(B, Tq, Tk, d, d, True)
+    q, k, v = (t.to(torch.bfloat16) for t in (Q, K, V))
+    outs = []
+    for _ in range(2):
+        o = torch.empty_like(q); lse = torch.empty(B, h, Tq, device="cuda")
+        assert lib.tsg_mha_fwd(ptr(q), ptr(k), ptr(v), ptr(o), None, None, ptr(lse), B, Tq, Tk, d, d, h, math.sqrt(d), 0, 0.0, 0, 0,
+                               TSG_BF16, st) == 0, lib.tsg_last_error()
+        outs.append(o)
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], outs[1])
+    _close(outs[0], _ref64(Q, K, V, gO, h, math.sqrt(d))[0].float().cpu(), "O")
+
+
+@pytest.mark.parametrize("mode,d,dv,h,Tq,Tk,p", [
+    ("f32s", 64, 64, 2, 128, 32, 0.0),      # head width 32, one key tile, one query block: the fused one-tile kernel stores dK / dV
+    ("f32s", 64, 64, 2, 129, 32, 0.0),      # two query blocks: zero fill, dK / dV added with atomics
+    ("f32s", 64, 64, 2, 40, 33, 0.0),       # two key tiles, wider than the head: the dK/dV + dQ pair
+    ("f32s", 128, 128, 2, 40, 64, 0.0),     # head width 64: Tk = 64 dS-once,
+    ("f32s", 128, 128, 2, 40, 65, 0.0),     # Tk = 65 the pair
+    ("f32s", 256, 256, 2, 40, 128, 0.0),    # head width 128: Tk = 128 dS-once,
+    ("f32s", 256, 256, 2, 40, 129, 0.0),    # Tk = 129 the pair
+    ("f32s", 320, 320, 2, 70, 70, 0.0),     # head width 160: split forward DT 5, wide split backward
+    ("f32s", 320, 320, 2, 40, 20, 0.0),
+    ("f32s", 512, 512, 2, 70, 70, 0.0),     # head width 256: DT 8
+    ("f32s", 512, 512, 2, 40, 20, 0.0),
+    ("f32s", 576, 576, 2, 9, 5, 0.0),       # head width 288: VALU forward and backward
+    ("f32s", 80, 80, 2, 9, 5, 0.0),         # head width 40: the split kernels do not apply -> exact MFMA
+    ("f32s", 64, 32, 2, 9, 5, 0.0),         # d_value != d_key: exact MFMA
+    ("fp32", 256, 256, 2, 9, 5, 0.0),       # head width 128: exact MFMA, full-width form
+    ("fp32", 256, 256, 2, 40, 33, 0.0),
+    ("fp32", 264, 264, 2, 9, 5, 0.0),       # head width 132: exact MFMA, wide form
+    ("fp32", 264, 264, 2, 40, 33, 0.0),
+    ("fp32", 32, 32, 4, 9, 5, 0.0),         # head width 8: exact MFMA
+    ("fp32", 32, 32, 4, 40, 33, 0.0),
+    ("bf16", 64, 64, 2, 128, 32, 0.0),      # bf16 storage: the fused one-tile kernel with one query block,
+    ("bf16", 64, 64, 2, 129, 32, 0.0),      # dS-once with two (bf16 outputs may not add with atomics)
+    ("bf16", 256, 256, 2, 40, 128, 0.0),    # dS-once
+    ("bf16", 256, 256, 2, 40, 129, 0.0),    # the pair
+    ("f32s", 64, 64, 2, 128, 32, 0.2),      # one case of each backward kind with attention dropout: one-tile,
+    ("f32s", 128, 128, 2, 40, 64, 0.2),     # dS-once,
+    ("f32s", 64, 64, 2, 40, 33, 0.2),       # pair,
+    ("f32s", 320, 320, 2, 40, 20, 0.2),     # wide split,
+    ("fp32", 256, 256, 2, 40, 33, 0.2),     # exact MFMA,
+    ("fp32", 264, 264, 2, 40, 33, 0.2),     # exact MFMA wide,
+    ("f32s", 576, 576, 2, 9, 5, 0.2),       # VALU
+    ("maps", 32, 32, 4, 9, 5, 0.0),         # strict fp32 with the A_forward maps: VALU forward
+    ("bf16-lib", 320, 320, 2, 40, 20, 0.0),  # bf16 storage at head widths 160 / 256: split forward DT 5 / 8 (forward only)
+    ("bf16-lib", 512, 512, 2, 40, 20, 0.0),
+])
+def test_mha_dispatch_edges(mode, d, dv, h, Tq, Tk, p):
+    """Present behaviour on either side of every boundary of plan_fwd / plan_bwd (csrc/mha.hip): float64 autograd of the formula at
+    the suite's own bounds (test_mha_split_precision for f32s, test_mha_parity for strict fp32, test_mha_bf16_storage for bf16
+    storage against the same bf16-valued inputs), and bitwise repeatability where include/tsg_hip.h promises it."""
+    if mode == "maps":
+        _edge_maps()
+    elif mode == "bf16-lib":
+        _edge_bf16_lib(d)
+    else:
+        _edge_check(mode, d, dv, h, Tq, Tk, p)
+
+
+@pytest.mark.parametrize("env", [{"TSG_MHA_SPLIT": "0"}, {"TSG_K2_BWD": "pair"}])
+def test_mha_ab_switches(env):
+    """K2's A/B switches are read once per process, so each runs in a child, on the two dS-once edge shapes and one one-tile shape.
+    TSG_MHA_SPLIT=0: the f32s mode runs the exact kernels -- the same bits as the strict fp32 mode.  TSG_K2_BWD=pair: the dK/dV + dQ
+    pair where dS-once would run -- f32s and bf16 storage at the bounds of test_mha_dispatch_edges."""
+    import os, subprocess, sys
+    code = r'''
+import os, torch
+from test_mha_gpu import _edge_check, _edge_inputs, _edge_run
+for (d, Tq, Tk) in ((128, 40, 64), (256, 40, 128), (64, 128, 32)):
+    if os.environ.get("TSG_MHA_SPLIT") == "0":
+        Q, K, V, gO = _edge_inputs(1, Tq, Tk, d, d, False)
+        o_s, g_s = _edge_run("f32s", Q, K, V, gO, 2)
+        o_e, g_e = _edge_run("fp32", Q, K, V, gO, 2)
+        assert torch.equal(o_s, o_e) and all(torch.equal(a, b) for a, b in zip(g_s, g_e)), (d, Tq, Tk)
+    else:
+        _edge_check("f32s", d, d, 2, Tq, Tk)
+        _edge_check("bf16", d, d, 2, Tq, Tk)
+print("ok")
+'''
+    here = os.path.dirname(os.path.abspath(__file__))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(here), here]), **env),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
