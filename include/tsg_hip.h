@@ -289,7 +289,9 @@ int tsg_lstm_set_l2_exchange(int on);
  * default, or TSG_LSTM_PERSIST).  The Python host selects 0 when its start-up self-test fails in both exchange modes.  */
 int tsg_lstm_set_persist(int mode);
 
-/* backward of the recurrence: dOut [T,B,2h] (+ optional dHn [2,B,h] added at each direction's last step)
+/* backward of the recurrence: dOut [T,B,2h] (+ optional dHn [2,B,h], the gradient of each direction's LAST hidden state -- nn.LSTM's
+ * h_n: dHn[0] joins dOut[T-1][:, 0:h], the forward direction's last step, and dHn[1] joins dOut[0][:, h:2h], the reverse direction's
+ * last step, which is time index 0; both are the first step the backward processes)
  * -> dG [T,B,2,4h] = dL/d(pre-activation gates); the caller derives dX, dW_ih, dW_hh, db from it with
  * GEMMs.  WhhT [2,h,4h] is W_hh transposed per direction; dC_ws is a [2,B,h] float workspace (the cell-gradient carry
  * between the per-step launches).                                                                            */
