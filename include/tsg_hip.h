@@ -46,7 +46,8 @@ extern "C" {
                            6: tsg_lstm_fwd_ws (the persistent LSTM forward's exchange ring in a caller-owned workspace), tsg_gemm_bf16, tsg_adam_step,
                               tsg_gemm_f32s_nn_acc, tsg_lstm_set_ring / _wide, tsg_wgrad_set_stream_k
                            7: tsg_time_next_launch / tsg_timed_launch_us (one launch bracketed by its own event pair), tsg_grads_nonfinite;
-                              tsg_scdm_long_* (K1 / K1g for sentences of up to tsg_scdm_long_max_words() words) added without a new revision */
+                              tsg_scdm_long_* (K1 / K1g for sentences of up to tsg_scdm_long_max_words() words) and tsg_boundary_head_tall_gemm /
+                              tsg_tall_bwd_combine (the boundary head on TALL's fusion) added without a new revision */
 #define TSG_F32 0
 #define TSG_BF16 1   /* bf16 storage of the activations, fp32 arithmetic (see Conventions)                               */
 #define TSG_F32S 2   /* fp32 storage; matrix products as split-precision bf16 MFMAs (x = hi + lo; hi*hi + hi*lo + lo*hi,
@@ -471,6 +472,22 @@ int tsg_match_head_gemm(const void* x, long long ldx, const void* w, long long l
 int tsg_boundary_head_gemm(const void* x, long long ldx, const void* w_start, const void* w_end, long long ldw, const void* cs,
                            const void* b1, const void* w2, const void* b2, const void* gate, const int32_t* mask, void* y,
                            void* p_start, void* p_end, void* ws, long long ws_bytes, int B, int T, int Hm, int K, void* stream);
+/* The boundary head on TALL's fusion (CrossModalInteraction.py:49-67: x_t = [v_t, s, v_t * s, v_t + s], W1 = [W_a | W_b | W_c | W_d],
+ * four [Hm,Dv] column blocks of each head's [Hm,4 Dv] parameter) without the [B,T,4 Dv] tensor:
+ *   W1 x_t = (W_a + W_d) v_t + W_c (v_t * s_b) + (W_b + W_d) s_b
+ * i.e. tsg_boundary_head_gemm over the virtual contraction [v | v * s_b] of 2 Dv columns -- the loader reads x a second time, scales it
+ * column-wise by the row's sentence vector in fp32 (one rounding) and splits the product.  K = Dv; x [B*T,K] (ldx); wv [2Hm,K] CONTIGUOUS
+ * = [W_a + W_d of start ; of end]; w_start_c / w_end_c [Hm,K]: the W_c blocks read in place (row stride ldw = 4 Dv for the parameters);
+ * sent [B,K] contiguous; cs [B,2Hm] = sent (W_b + W_d)^T; everything else, the checks (with K), the workspace
+ * (tsg_head_gemm_ws_bytes(B*T, 2Hm, 2)), the optional y and the trailing softmax as tsg_boundary_head_gemm.  Row tiles: 128 / 64.
+ * tsg_tall_bwd_combine finishes the two input-gradient products of that GEMM (dv0 = dy wv, u = dy [w_start_c ; w_end_c], both [B,T,D]):
+ *   dv += u * s_b;  ds[b,k] = sum_t u[b,t,k] v[b,t,k] (fixed order, no atomics);  u <- v * s_b (the operand of the W_c weight gradient).
+ *   u, v, dv [B,T,D], s, ds [B,D] fp32 contiguous, 16-byte aligned; D % 4 == 0, T arbitrary.                                          */
+int tsg_boundary_head_tall_gemm(const void* x, long long ldx, const void* wv, const void* w_start_c, const void* w_end_c, long long ldw,
+                                const void* sent, const void* cs, const void* b1, const void* w2, const void* b2, const void* gate,
+                                const int32_t* mask, void* y, void* p_start, void* p_end, void* ws, long long ws_bytes, int B, int T,
+                                int Hm, int K, void* stream);
+int tsg_tall_bwd_combine(void* u, const void* v, const void* s, void* dv, void* ds, int B, int T, int D, void* stream);
 /* softmax over T of two [B,T] logit tensors, in place (the second kernel of tsg_boundary_score_fwd, exported for the fused head) */
 int tsg_boundary_softmax(void* p_start, void* p_end, int B, int T, void* stream);
 

@@ -82,6 +82,8 @@ _SIGNATURES = {
     "tsg_head_gemm_ws_bytes": [_I, _I, _I],
     "tsg_match_head_gemm": [_P, c_longlong, _P, c_longlong, _P, _P, _P, _P, _P, _P, c_longlong, _I, _I, _I, _I, _I, _P],
     "tsg_boundary_head_gemm": [_P, c_longlong, _P, _P, c_longlong] + [_P] * 10 + [c_longlong, _I, _I, _I, _I, _P],
+    "tsg_boundary_head_tall_gemm": [_P, c_longlong, _P, _P, _P, c_longlong] + [_P] * 11 + [c_longlong, _I, _I, _I, _I, _P],
+    "tsg_tall_bwd_combine": [_P] * 5 + [_I, _I, _I, _P],
     "tsg_boundary_softmax": [_P, _P, _I, _I, _P],
     "tsg_transpose_f32": [_P, c_longlong, _P, _I, _I, _I, _P],
     "tsg_dropout": [_P, _P, c_longlong, c_float, c_uint64, c_uint64, _P, _P, _I, _I, _P],

@@ -442,6 +442,44 @@ int check(const char* fn, int B, int T, int Hm, int dtype) {
   return 0;
 }
 
+// ---- TALL's fusion, backward glue (tsg_tall_bwd_combine).  The head GEMM of tsg_boundary_head_tall_gemm runs over [v | v * s_b]; its two
+// input-gradient products are dv0 = dy Wv and U = dy [W_c start ; W_c end].  One pass finishes them:
+//     dv += U * s_b        ds[b,k] = sum_t U[b,t,k] v[b,t,k]        U <- v * s_b   (the second operand of the W_c weight gradient)
+// Workgroup = (item, 128-column slice): 32 lanes own a float4 of columns each, the 8 lane groups take t = g, g + 8, ...; the ds partials
+// meet in LDS and are added in group order: run-to-run identical, no float atomics.  T arbitrary, D % 4 == 0.
+constexpr int kCombThreads = 256, kCombQuads = 32, kCombGroups = kCombThreads / kCombQuads;
+
+__global__ __launch_bounds__(kCombThreads) void tall_bwd_combine_kernel(float* __restrict__ u, const float* __restrict__ v,
+                                                                        const float* __restrict__ s, float* __restrict__ dv,
+                                                                        float* __restrict__ ds, int T, int D, int slices) {
+  __shared__ float4 part[kCombGroups][kCombQuads];
+  const int b = blockIdx.x / slices, c0 = (blockIdx.x % slices) * (4 * kCombQuads);
+  const int q = threadIdx.x % kCombQuads, g = threadIdx.x / kCombQuads;
+  const int col = c0 + 4 * q;
+  const bool live = col < D;                                      // (D % 4 == 0: a live quad is whole)
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live) {
+    const float4 sv = ld4(s + (size_t)b * D + col);
+    for (int t = g; t < T; t += kCombGroups) {
+      const size_t o = ((size_t)b * T + t) * D + col;
+      const float4 uv = ld4(u + o), vv = ld4(v + o);
+      float4 d = ld4(dv + o);
+      d.x = fmaf(uv.x, sv.x, d.x); d.y = fmaf(uv.y, sv.y, d.y); d.z = fmaf(uv.z, sv.z, d.z); d.w = fmaf(uv.w, sv.w, d.w);
+      acc.x = fmaf(uv.x, vv.x, acc.x); acc.y = fmaf(uv.y, vv.y, acc.y); acc.z = fmaf(uv.z, vv.z, acc.z); acc.w = fmaf(uv.w, vv.w, acc.w);
+      st4(dv + o, d);
+      st4(u + o, make_float4(vv.x * sv.x, vv.y * sv.y, vv.z * sv.z, vv.w * sv.w));
+    }
+  }
+  part[g][q] = acc;
+  __syncthreads();
+  if (g == 0 && live) {
+    float4 r = part[0][q];
+#pragma unroll
+    for (int i = 1; i < kCombGroups; ++i) { const float4 p = part[i][q]; r.x += p.x; r.y += p.y; r.z += p.z; r.w += p.w; }
+    st4(ds + (size_t)b * D + col, r);
+  }
+}
+
 }  // namespace
 }  // namespace tsg
 
@@ -564,5 +602,19 @@ extern "C" int tsg_boundary_score_bwd_ws(const void* y, const void* cs, const vo
                        (const float*)dp_start, (const float*)dp_end, (float*)dy, (float*)dcs, (float*)db1_part,
                        (float*)dw2_part, (float*)db2_part, (float*)dgate, part, cnt, B, T, Hm, cgs);
   }
+  return check_launch(fn);
+}
+
+extern "C" int tsg_tall_bwd_combine(void* u, const void* v, const void* s, void* dv, void* ds, int B, int T, int D, void* stream) {
+  const char* fn = "tsg_tall_bwd_combine";
+  for (const void* p : {(const void*)u, v, s, (const void*)dv, (const void*)ds}) {
+    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
+    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
+  }
+  if (B <= 0 || T <= 0 || D <= 0 || D % 4) return set_error(TSG_E_SHAPE, "%s: bad B=%d T=%d D=%d (D must be a multiple of 4)", fn, B, T, D);
+  const int slices = cdiv(D, 4 * kCombQuads);
+  if ((long long)B * slices > 0x7fffffffLL) return set_error(TSG_E_SHAPE, "%s: B=%d x %d column slices exceed the grid", fn, B, slices);
+  hipLaunchKernelGGL(tall_bwd_combine_kernel, dim3(B * slices), dim3(kCombThreads), 0, static_cast<hipStream_t>(stream),
+                     (float*)u, (const float*)v, (const float*)s, (float*)dv, (float*)ds, T, D, slices);
   return check_launch(fn);
 }

@@ -247,10 +247,41 @@ struct EpiHead {
 // row-wise as 4 x 4 blocks and TRANSPOSED on the way into the same LDS image (four 8-byte pieces per thread and plane: the staging of
 // the weight-gradient kernel, csrc/wgrad_split.hip); nothing else changes.  It replaces a transposed copy of the weight per call
 // (16 MB for an LSTM layer's W_ih, 4 MB for a d x d projection).  In this mode the two segments (W0 | W1, nseg) split the ROWS.
-template <int TM, typename Epi, bool WT = false>
+//
+// XOp: what the loader does to the X operand on its way into the planes.
+//   XPlain     nothing (every GEMM above).
+//   XScaleSeg  TALL's fusion inside the boundary head (CrossModalInteraction.py:49-67: x_t = [v_t, s, v_t * s, v_t + s]):
+//                W1 x_t = (W_a + W_d) v_t + W_c (v_t * s_b) + (W_b + W_d) s_b
+//              so the GEMM runs over a VIRTUAL contraction of 2 kseg columns: chunks below kseg are X against W0 | W1 as they are,
+//              chunks from kseg on read X at column k0 - kseg, scale it column-wise by the row's own sentence vector s[b, :] (one
+//              fp32 rounding, then the split) and take W from a second pair of row segments (w0c | w1c, row stride ldwc: the W_c
+//              blocks of the start / end parameters in place).  A chunk lies in one segment (kseg % 32 == 0); the K loop runs as
+//              one loop per segment with compile-time tags, so each steady-state chunk body stays one basic block.
+struct XPlain { static constexpr bool kSeg = false; };
+struct XScaleSeg {
+  static constexpr bool kSeg = true;
+  const float* s;                  // [M / T, kseg], row stride kseg
+  const float* w0c; const float* w1c; long long ldwc;
+  int kseg, T;
+};
+__device__ __forceinline__ float g_mul_rn(float a, float b) {          // a * b rounded to fp32: never contracted into the split's subtraction
+  float p = a * b;
+  asm("" : "+v"(p));
+  return p;
+}
+
+// The prologue is a TRAILING PACK of the kernel (empty = XPlain, else the one XOp object): with no prologue the kernel keeps the argument
+// block it had, down to the offsets of the hidden arguments.
+template <typename... A> struct XOpOf { typedef XPlain type; static __device__ __forceinline__ XPlain get() { return XPlain{}; } };
+template <typename A> struct XOpOf<A> { typedef A type; static __device__ __forceinline__ const A& get(const A& a) { return a; } };
+
+template <int TM, typename Epi, bool WT = false, typename... XArg>
 __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ W0,
                                                            const float* __restrict__ W1, int nseg, long long ldw, Epi epi,
-                                                           int M, int N, int K, int tiles_n) {
+                                                           int M, int N, int K, int tiles_n, XArg... xarg) {
+  typedef typename XOpOf<XArg...>::type XOp;
+  const XOp xop = XOpOf<XArg...>::get(xarg...);
+  static_assert(!(WT && XOp::kSeg), "the scaled segment is staged row-wise");
   constexpr int MI = TM / 64, PX = TM / 64;                         // MFMA row tiles per wave; staging passes over the X tile
   constexpr int kPlaneX = plane_x<TM>();
   constexpr int kBuf = 2 * kPlaneX + 2 * kPlaneW;
@@ -288,6 +319,29 @@ __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restri
   // WT staging role: a 4 (k) x 4 (n) block; lane bits [1:0] = column quad inside a 64-byte segment, [4:2] = row group, [5..8] = segment
   const int tmg = (tid >> 2) & 7, tc4 = (tid & 3) + 4 * (tid >> 5);
   float4 rx[PX], rw[4];
+  // XScaleSeg: the second segment's W rows and, per staging row, the sentence row of its batch item (a 64-row pass may span several items)
+  float4 rs[XOp::kSeg ? PX : 1];
+  const float* ssrc[XOp::kSeg ? PX : 1];
+  const float* wsrc2 = nullptr;
+  size_t passw2 = 0;
+  if constexpr (XOp::kSeg) {
+    wsrc2 = (n0 < nseg ? xop.w0c + (size_t)n0 * xop.ldwc : xop.w1c + (size_t)(n0 - nseg) * xop.ldwc) + (size_t)sr * xop.ldwc + 4 * sq;
+    passw2 = (size_t)64 * xop.ldwc;
+#pragma unroll
+    for (int p = 0; p < PX; ++p) ssrc[p] = xop.s + (size_t)((m0 + sr + 64 * p) / xop.T) * xop.kseg + 4 * sq;
+  }
+  auto request_scaled = [&](int k0) {                                  // XScaleSeg, chunks of the second segment
+    if constexpr (XOp::kSeg) {
+      const int kc = k0 - xop.kseg;
+#pragma unroll
+      for (int p = 0; p < PX; ++p) {
+        rx[p] = *reinterpret_cast<const float4*>(xsrc + p * passx + kc);
+        rs[p] = *reinterpret_cast<const float4*>(ssrc[p] + kc);
+      }
+#pragma unroll
+      for (int p = 0; p < 4; ++p) rw[p] = *reinterpret_cast<const float4*>(wsrc2 + p * passw2 + kc);
+    }
+  };
   auto request = [&](int k0) {
 #pragma unroll
     for (int p = 0; p < PX; ++p) rx[p] = *reinterpret_cast<const float4*>(xsrc + p * passx + k0);
@@ -339,6 +393,27 @@ __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restri
       }
     }
   };
+  // XScaleSeg, chunks of the second segment: x * s in fp32 (one rounding), then the split; W as above (row-wise staging)
+  auto write_planes_scaled = [&](int buf) {
+    if constexpr (XOp::kSeg) {
+      unsigned* base = lds + buf * kBuf;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int r = sr + 64 * p;
+        const int o = r * 16 + (((sq >> 1) ^ ((r >> 2) & 3)) << 2) + ((sq & 1) << 1);
+        unsigned h0, l0, h1, l1;
+        if (p < PX) {
+          const float4 xv = rx[p < PX ? p : 0], sv = rs[p < PX ? p : 0];
+          g_split_pair(g_mul_rn(xv.x, sv.x), g_mul_rn(xv.y, sv.y), h0, l0); g_split_pair(g_mul_rn(xv.z, sv.z), g_mul_rn(xv.w, sv.w), h1, l1);
+          *reinterpret_cast<uint2*>(base + o) = make_uint2(h0, h1);
+          *reinterpret_cast<uint2*>(base + kPlaneX + o) = make_uint2(l0, l1);
+        }
+        g_split_pair(rw[p].x, rw[p].y, h0, l0); g_split_pair(rw[p].z, rw[p].w, h1, l1);
+        *reinterpret_cast<uint2*>(base + 2 * kPlaneX + o) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(base + 2 * kPlaneX + kPlaneW + o) = make_uint2(l0, l1);
+      }
+    }
+  };
   // fragment of k step s: 8 consecutive k (one 16-byte piece 2 s + kg, swizzled) of row r, from the hi and the lo plane
   auto frag = [&](const unsigned* hi_plane, int plane, int r, int s, g_u32x4& hi, g_u32x4& lo) {
     const int o = r * 16 + (((2 * s + kg) ^ ((r >> 2) & 3)) << 2);
@@ -355,18 +430,16 @@ __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restri
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   const int nk = K / kBK;
-  request(0);
-  write_planes(0);                                                   // chunk 0 -> buffer 0
-  if (nk > 1) request(kBK);
   // chunk ks: buffer ks & 1 is multiplied; the registers hold chunk ks + 1, which is converted into the other buffer right after the
   // barrier, and chunk ks + 2 is requested into them.  WRITE / REQ are compile-time so that the steady-state body is one basic block
-  // (a branch inside it pins every fragment read in front of its own MFMAs).
+  // (a branch inside it pins every fragment read in front of its own MFMAs).  Tag values: 0 nothing, 1 plain / first segment,
+  // 2 the scaled second segment of XScaleSeg.
   auto chunk = [&](int ks, auto w_tag, auto r_tag) {
-    constexpr bool WRITE = decltype(w_tag)::value, REQ = decltype(r_tag)::value;
+    constexpr int WRITE = decltype(w_tag)::value, REQ = decltype(r_tag)::value;
     lds_barrier();                                                   // chunk ks is in LDS; nobody reads the other buffer any more
     __builtin_amdgcn_sched_barrier(0);                               // nothing of this chunk is scheduled in front of the barrier (2-4 %)
-    if (WRITE) write_planes((ks + 1) & 1);
-    if (REQ) request((ks + 2) * kBK);
+    if (WRITE == 2) write_planes_scaled((ks + 1) & 1); else if (WRITE) write_planes((ks + 1) & 1);
+    if (REQ == 2) request_scaled((ks + 2) * kBK); else if (REQ) request((ks + 2) * kBK);
     const unsigned* xt = lds + (ks & 1) * kBuf;
     const unsigned* wt = xt + 2 * kPlaneX;
 #pragma unroll
@@ -389,12 +462,38 @@ __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restri
       }
     }
   };
-  typedef std::true_type Y_; typedef std::false_type N_;
-  int ks = 0;
+  typedef std::integral_constant<int, 0> N_; typedef std::integral_constant<int, 1> Y_; typedef std::integral_constant<int, 2> S_;
+  if constexpr (XOp::kSeg) {
+    // nk = 2 n1 chunks: [0, n1) plain, [n1, 2 n1) scaled.  Chunk ks converts chunk ks + 1 and requests chunk ks + 2, so the tags change one
+    // and two chunks ahead of the segment switch; each steady-state loop keeps one pair of tags.
+    const int n1 = xop.kseg / kBK;
+    request(0);
+    write_planes(0);
+    int ks = 0;
+    if (n1 > 1) {
+      request(kBK);
 #pragma unroll 1
-  for (; ks + 2 < nk; ++ks) chunk(ks, Y_{}, Y_{});
-  if (ks + 1 < nk) { chunk(ks, Y_{}, N_{}); ++ks; }
-  chunk(ks, N_{}, N_{});
+      for (; ks + 2 < n1; ++ks) chunk(ks, Y_{}, Y_{});
+      chunk(ks, Y_{}, S_{}); ++ks;                                     // ks = n1 - 2: chunk n1 - 1 is the last plain one, chunk n1 the first scaled
+      chunk(ks, S_{}, S_{}); ++ks;                                     // ks = n1 - 1
+#pragma unroll 1
+      for (; ks + 2 < nk; ++ks) chunk(ks, S_{}, S_{});
+      chunk(ks, S_{}, N_{}); ++ks;                                     // ks = nk - 2
+    } else {                                                           // one chunk per segment
+      request_scaled(kBK);
+      chunk(ks, S_{}, N_{}); ++ks;
+    }
+    chunk(ks, N_{}, N_{});
+  } else {
+    request(0);
+    write_planes(0);                                                 // chunk 0 -> buffer 0
+    if (nk > 1) request(kBK);
+    int ks = 0;
+#pragma unroll 1
+    for (; ks + 2 < nk; ++ks) chunk(ks, Y_{}, Y_{});
+    if (ks + 1 < nk) { chunk(ks, Y_{}, N_{}); ++ks; }
+    chunk(ks, N_{}, N_{});
+  }
   if (Epi::kUsesLds) __syncthreads();                                // every wave is done with the last chunk's buffer: the epilogue reuses LDS
   const TilePos pos{m0, n0, wm, wn, jl, kg, tid};
   epi.template run<MI>(acc, pos, reinterpret_cast<float*>(lds));
@@ -412,17 +511,18 @@ __global__ __launch_bounds__(kGT) void gemm_nt_f32s_kernel(const float* __restri
 // profiles/r4/gemm_f32s_mfma_shape_ab_v1.txt.  The LDS image for its fragment reads: piece p of row r at slot p ^ h((r >> 2) & 3),
 // h = {0, 3, 2, 1}, conflict-free for both the b128 reads and the staging writes.)
 
-template <int TM, typename Epi, bool WT = false>
+// xop: nothing, or the one X-operand prologue object (it becomes the kernel's trailing argument)
+template <int TM, typename Epi, bool WT = false, typename... XArg>
 int launch_gemm(const char* fn, const float* x, long long ldx, const float* w0, const float* w1, int nseg, long long ldw, const Epi& epi,
-                int M, int N, int K, hipStream_t st) {
-  auto kern = gemm_nt_f32s_kernel<TM, Epi, WT>;
+                int M, int N, int K, hipStream_t st, const XArg&... xop) {
+  auto kern = gemm_nt_f32s_kernel<TM, Epi, WT, XArg...>;
   constexpr size_t lds = gemm_lds<TM>();
   hipError_t e = allow_lds(kern, lds);
   if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute(%zu): %s", fn, lds, hipGetErrorString(e));
   const int tiles_n = N / kTN;
   const int tiles = (M / TM) * tiles_n, cus = device_cu_count();
   const int grid = tiles < cus ? tiles : cus;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(kGT), lds, st, x, ldx, w0, w1, nseg, ldw, epi, M, N, K, tiles_n);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(kGT), lds, st, x, ldx, w0, w1, nseg, ldw, epi, M, N, K, tiles_n, xop...);
   return check_launch(fn);
 }
 
@@ -430,11 +530,11 @@ int launch_gemm(const char* fn, const float* x, long long ldx, const float* w0, 
 // time per 1024 columns of K, measured at one tile per CU (tools/gemm_small_time.py): 73 / 46 / 31 us -- the W tile (256 x 32 per chunk)
 // is converted by every workgroup whatever its M, so small tiles pay off only while they save a round or fill idle CUs:
 // [2560 x 1024] x [1024 x 1024]^T 70 / 47 / 33 us, [8192 x 1024] x [1024 x 1024]^T 77 / 57 / 69 us, [1280 x 1024] x [4096 x 1024]^T 74 / 53 / 67 us.
-inline int pick_tm(int M, int N) {
+inline int pick_tm(int M, int N, int tm_max = 256) {
   const int cus = device_cu_count(), tiles_n = N / kTN;
   int best = 0; float best_cost = 0.f;
   for (int tm : {256, 128, 64}) {
-    if (M % tm) continue;
+    if (M % tm || tm > tm_max) continue;
     const int tiles = (M / tm) * tiles_n;
     const float cost = (float)((tiles + cus - 1) / cus) * (17.f + 0.22f * tm);
     if (!best || cost < best_cost) { best = tm; best_cost = cost; }
@@ -587,4 +687,43 @@ extern "C" int tsg_boundary_head_gemm(const void* x, long long ldx, const void* 
   else rc = launch_gemm<64>(fn, xf, ldx, (const float*)w_start, (const float*)w_end, Hm, ldw, epi, M, N, K, st);
   if (rc) return rc;
   return tsg_boundary_softmax(p_start, p_end, B, T, stream);       // softmax over T, in place (csrc/boundary_head.hip)
+}
+
+// The boundary head on TALL's fusion (XScaleSeg above): K = Dv, the GEMM runs over the virtual contraction 2 Dv.
+extern "C" int tsg_boundary_head_tall_gemm(const void* x, long long ldx, const void* wv, const void* w_start_c, const void* w_end_c,
+                                           long long ldw, const void* sent, const void* cs, const void* b1, const void* w2, const void* b2,
+                                           const void* gate, const int32_t* mask, void* y, void* p_start, void* p_end, void* ws,
+                                           long long ws_bytes, int B, int T, int Hm, int K, void* stream) {
+  const char* fn = "tsg_boundary_head_tall_gemm";
+  if (B <= 0 || T <= 0 || (long long)B * T > (1 << 22)) return set_error(TSG_E_SHAPE, "%s: bad B=%d T=%d", fn, B, T);
+  if (K > (1 << 29)) return set_error(TSG_E_SHAPE, "%s: K=%d too large", fn, K);
+  const int M = B * T, N = 2 * Hm;
+  // (checked with K = Dv: both halves of the contraction read Dv columns of x, wv and the W_c blocks; 2 Dv % 32 == 0 follows)
+  int rc = check_head(fn, {x, wv, w_start_c, w_end_c, sent, cs, b1, w2, b2, (const void*)p_start, (const void*)p_end, (const void*)ws},
+                      M, T, N, K, ldx, ldw, Hm);
+  if (rc) return rc;
+  if (y && !aligned16(y)) return set_error(TSG_E_ALIGN, "%s: y not 16-byte aligned", fn);
+  if (T > 8192) return set_error(TSG_E_SHAPE, "%s: T=%d > 8192 not supported", fn, T);
+  if (ws_bytes < head_ws_bytes(M, N, 2)) return set_error(TSG_E_SHAPE, "%s: workspace of %lld B < %lld B (tsg_head_gemm_ws_bytes)", fn, ws_bytes, head_ws_bytes(M, N, 2));
+  auto st = static_cast<hipStream_t>(stream);
+  // Row tiles of 128 / 64 only: with the sentence float4 per staging pass beside the X one, the 256-row instantiation spills (280 B of scratch
+  // per lane); the head's shapes take the small tiles anyway ([8192 x 512]: 64 rows, [15360 x 512]: 128 rows under pick_tm's cost).
+  const int tm = pick_tm(M, N, 128);
+  const long long cntw = roundup((long long)2 * (M / 64), 4);
+  unsigned* cnt = static_cast<unsigned*>(ws);
+  float* part = static_cast<float*>(ws) + cntw;
+  if (Hm / kTN > 1) {
+    hipError_t e = zero_async(cnt, sizeof(unsigned) * cntw, st);
+    if (e != hipSuccess) return set_error((int)e, "%s: zero fill: %s", fn, hipGetErrorString(e));
+  }
+  const HeadArgs a{(const float*)cs, (const float*)b1, (const float*)w2, (const float*)b2, (const float*)gate, mask, (float*)y,
+                   (float*)p_start, (float*)p_end, part, cnt, M, N, T, Hm, 1.f / (float)T};
+  const EpiHead<1, 1> epi{a};
+  const XScaleSeg xop{(const float*)sent, (const float*)w_start_c, (const float*)w_end_c, ldw, K, T};
+  const float* xf = (const float*)x;
+  const float* wv0 = (const float*)wv; const float* wv1 = wv0 + (size_t)Hm * K;      // [start ; end] rows of Wv, contiguous
+  if (tm == 128) rc = launch_gemm<128>(fn, xf, ldx, wv0, wv1, Hm, K, epi, M, N, 2 * K, st, xop);
+  else rc = launch_gemm<64>(fn, xf, ldx, wv0, wv1, Hm, K, epi, M, N, 2 * K, st, xop);
+  if (rc) return rc;
+  return tsg_boundary_softmax(p_start, p_end, B, T, stream);
 }

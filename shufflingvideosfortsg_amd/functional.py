@@ -1143,6 +1143,12 @@ def head_gemm_ok(M: int, N: int, K: int, T: int, head_width: int) -> bool:
             and 0 < T <= 8192 and M % T == 0 and M <= (1 << 22))
 
 
+def tall_head_ok(B: int, T: int, Dv: int, Ds: int, Hm: int) -> bool:
+    """Shapes tsg_boundary_head_tall_gemm takes (TALL's fusion inside the boundary head): the head GEMM's rule over the virtual contraction
+    2 Dv, one width for clips and sentence, and whole 32-column chunks per segment of the contraction."""
+    return Dv == Ds and Dv % 32 == 0 and head_gemm_ok(B * T, 2 * Hm, 2 * Dv, T, Hm)
+
+
 class GradSink:
     """The gradient of ONE activation with several consumers (the final clip features of GMD: matching head, boundary head on the leading rows,
     temporal-order discriminator -- SpanGroundMatchDisc.py:80-96), summed inside the consumers' own kernels: the first consumer to run its
@@ -1491,7 +1497,10 @@ class _BoundaryHeadFull(torch.autograd.Function):
         Ws, We, sent = _f32p(Ws), _f32p(We), _f32p(sent)
         if We.shape != Ws.shape or Ws.stride(0) != We.stride(0) or Ws.stride(0) % 4 or Ws.data_ptr() % 16 or We.data_ptr() % 16 or Dv % 4:
             raise ValueError("boundary_head: the two first Linears must be [Hm, Dv+Ds] row-major parameters of one shape")
-        cs = torch.cat([sent @ Ws[:, Dv:].t(), sent @ We[:, Dv:].t()], 1)              # [B,2Hm]: sentence half (b1 is added in the kernel)
+        if Ws.shape[1] == Dv:                                                            # OnlyVideo: no sentence columns
+            cs = x.new_zeros(B, J)
+        else:
+            cs = torch.cat([sent @ Ws[:, Dv:].t(), sent @ We[:, Dv:].t()], 1)          # [B,2Hm]: sentence half (b1 is added in the kernel)
         pack = torch.cat([t.reshape(-1).to(torch.float32) for t in (bs, be, w2s, w2e, b2s, b2e)])
         b1, w2, b2 = pack[:J], pack[J:2 * J], pack[2 * J:2 * J + 2]
         gate_c = _f32p(gate) if gate is not None else None
@@ -1542,13 +1551,15 @@ class _BoundaryHeadFull(torch.autograd.Function):
                 pass                                                     # added onto the shared activation's gradient rows: None for autograd
             else:
                 dx = _dx_f32s(dy2, torch.cat([ws_, we_], 0)).view(B, T, Dv)
-        dsent = torch.addmm(dcs[:, :Hm] @ Ws[:, Dv:], dcs[:, Hm:], We[:, Dv:]) if ctx.needs_input_grad[1] else None
+        has_sent = Ws.shape[1] > Dv
+        dsent = torch.addmm(dcs[:, :Hm] @ Ws[:, Dv:], dcs[:, Hm:], We[:, Dv:]) if ctx.needs_input_grad[1] and has_sent else None
         dWs = dWe = None
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
             dW = torch.empty(2, Hm, Ws.shape[1], device=y.device, dtype=torch.float32)       # [start ; end], full width
             dW2 = dW.view(J, Ws.shape[1])
             _dw_f32s(dy2, x2, out=dW2[:, :Dv])
-            dW2[:, Dv:] = dcs.t() @ sent
+            if has_sent:
+                dW2[:, Dv:] = dcs.t() @ sent
             dWs, dWe = dW[0], dW[1]
         db1, dw2, db2 = db1p.sum(0), dw2p.sum(0), db2p.sum(0)
         s2s, s2e = ctx.shapes
@@ -1558,6 +1569,114 @@ class _BoundaryHeadFull(torch.autograd.Function):
 def boundary_head_params(x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate=None, mask=None):
     """Boundary head from its parameters (tsg_boundary_head_gemm; see _BoundaryHeadFull)."""
     return _BoundaryHeadFull.apply(x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate, mask, _sink_for(x))
+
+
+def boundary_head_video_params(x, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate=None, mask=None):
+    """Boundary head on the clip features alone (OnlyVideo + MLP_predictor): ``boundary_head_params`` with [Hm, Dv] first Linears, no sentence
+    columns and a zero per-item row."""
+    return _BoundaryHeadFull.apply(x, x.new_zeros(x.shape[0], 0), Ws, bs, We, be, w2s, b2s, w2e, b2e, gate, mask, _sink_for(x))
+
+
+class _BoundaryHeadTall(torch.autograd.Function):
+    """The boundary head on TALL's fusion x_t = [v_t, s, v_t * s, v_t + s] (reference CrossModalInteraction.py:49-67 + SpanPredictor.py:71-85,
+    gate SpanGroundMatchDisc.py:86) with the MODULE'S PARAMETERS as inputs: x [B,T,d], sent [B,d], first Linears W = [W_a | W_b | W_c | W_d]
+    [Hm,4d] per head.  W x_t = (W_a + W_d) v_t + W_c (v_t * s) + (W_b + W_d) s: the head GEMM runs over [v | v * s] with the scaling in its
+    loader (tsg_boundary_head_tall_gemm; W_c read in place), the sentence term is a per-item row.  Backward: dy as in _BoundaryHeadFull; the
+    two input-gradient GEMMs dy Wv and U = dy W_c, tsg_tall_bwd_combine (dv += U * s, ds = sum_t U * v, U <- v * s), and the weight-gradient
+    kernel writes dW_a and dW_c in place into the full-width dW.  Nothing wider than [B,T,d] / [B,T,2Hm] exists in either direction."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate, mask, sink=None):
+        require_device(x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate, mask)
+        ctx.sink, ctx.x_in = sink, (x if sink is not None else None)
+        x = _f32c(x)
+        B, T, d = x.shape
+        Hm, J = Ws.shape[0], 2 * Ws.shape[0]
+        Ws, We, sent = _f32p(Ws), _f32p(We), _f32p(sent)
+        if (Ws.shape != (Hm, 4 * d) or We.shape != Ws.shape or not Ws.is_contiguous() or not We.is_contiguous() or Ws.data_ptr() % 16
+                or We.data_ptr() % 16 or sent.shape != (B, d) or d % 4):
+            raise ValueError("boundary_head_tall: the two first Linears must be contiguous [Hm, 4 d] parameters, x [B,T,d] and sent [B,d]")
+        Wv = torch.cat([Ws[:, :d] + Ws[:, 3 * d:], We[:, :d] + We[:, 3 * d:]], 0)                     # [2Hm,d]: W_a + W_d, fp32
+        Wbd = torch.cat([Ws[:, d:2 * d] + Ws[:, 3 * d:], We[:, d:2 * d] + We[:, 3 * d:]], 0)          # [2Hm,d]: W_b + W_d
+        cs = sent @ Wbd.t()                                                                           # [B,2Hm] (b1 is added in the kernel)
+        pack = torch.cat([t.reshape(-1).to(torch.float32) for t in (bs, be, w2s, w2e, b2s, b2e)])
+        b1, w2, b2 = pack[:J], pack[J:2 * J], pack[2 * J:2 * J + 2]
+        gate_c = _f32p(gate) if gate is not None else None
+        mask_c = mask.to(torch.int32).contiguous() if mask is not None else None
+        need_y = any(ctx.needs_input_grad[:11])
+        y = torch.empty(B, T, J, device=x.device, dtype=torch.float32) if need_y else None
+        ps = torch.empty(B, T, device=x.device, dtype=torch.float32)
+        pe = torch.empty_like(ps)
+        nb = int(load().tsg_head_gemm_ws_bytes(B * T, J, 2))
+        wsb = torch.empty(max(nb, 16), device=x.device, dtype=torch.uint8)
+        _call("tsg_boundary_head_tall_gemm", x, ptr(x), d, ptr(Wv), ptr(Ws) + 8 * d, ptr(We) + 8 * d, 4 * d, ptr(sent), ptr(cs), ptr(b1),
+              ptr(w2), ptr(b2), ptr(gate_c) if gate_c is not None else None, ptr(mask_c) if mask_c is not None else None,
+              ptr(y) if need_y else None, ptr(ps), ptr(pe), ptr(wsb), nb, B, T, Hm, d)
+        if need_y:
+            ctx.save_for_backward(x, sent, Ws, We, Wv, Wbd, y, cs, b1, w2, ps, pe, *([gate_c] if gate_c is not None else []),
+                                  *([mask_c] if mask_c is not None else []))
+        ctx.has_gate, ctx.has_mask = gate_c is not None, mask_c is not None
+        ctx.shapes = (w2s.shape, w2e.shape)
+        return ps, pe
+
+    @staticmethod
+    @_bwd
+    def backward(ctx, dps, dpe):
+        saved = list(ctx.saved_tensors)
+        x, sent, Ws, We, Wv, Wbd, y, cs, b1, w2, ps, pe = saved[:12]
+        rest = saved[12:]
+        gate = rest.pop(0) if ctx.has_gate else None
+        mask = rest.pop(0) if ctx.has_mask else None
+        B, T, J = y.shape
+        d, Hm = x.shape[2], J // 2
+        M = B * T
+        dps = _f32p(dps) if dps is not None else torch.zeros_like(ps)
+        dpe = _f32p(dpe) if dpe is not None else torch.zeros_like(pe)
+        dy = torch.empty_like(y); dcs = torch.empty_like(cs)
+        db1p = torch.empty(B, J, device=y.device, dtype=torch.float32)
+        dw2p = torch.empty_like(db1p)
+        db2p = torch.empty(B, 2, device=y.device, dtype=torch.float32)
+        dgate = torch.empty(B, T, device=y.device, dtype=torch.float32) if gate is not None else None
+        wk, nb = _k3_workspace(y.device, B, T, Hm)
+        _k3_call("tsg_boundary_score_bwd_ws", y, ptr(y), ptr(cs), ptr(b1), ptr(w2),
+              ptr(gate) if gate is not None else None, ptr(mask) if mask is not None else None,
+              ptr(ps), ptr(pe), ptr(dps), ptr(dpe), ptr(dy), ptr(dcs), ptr(db1p), ptr(dw2p), ptr(db2p),
+              ptr(dgate) if dgate is not None else None, ptr(wk), nb, B, T, Hm, TSG_F32)
+        dy2, x2 = dy.view(M, J), x.view(M, d)
+        wcs, wce = Ws[:, 2 * d:3 * d], We[:, 2 * d:3 * d]                  # the W_c blocks, in place
+        dx = dsent = dWs = dWe = None
+        if any(ctx.needs_input_grad[i] for i in (0, 1, 2, 4)):
+            nn_ok = gemm_f32s_nn_ok(M, d, J)
+            U = gemm_f32s_nn(dy2, wcs, wce) if nn_ok else _dx_f32s(dy2, torch.cat([wcs, wce], 0))
+            in_sink = False
+            if ctx.needs_input_grad[0] and ctx.sink is not None and _sink_add_dx(ctx.sink, ctx.x_in, dy2, Wv[:Hm], Wv[Hm:]):
+                r0, r1 = ctx.sink.rows(ctx.x_in)
+                dv, in_sink = ctx.sink.buf[r0:r1].view(M, d), True        # dy Wv sits on the shared activation's gradient rows; the combine adds there
+            else:
+                dv = gemm_f32s_nn(dy2, Wv[:Hm], Wv[Hm:]) if nn_ok else _dx_f32s(dy2, Wv)
+            ds = torch.empty(B, d, device=y.device, dtype=torch.float32)
+            _call("tsg_tall_bwd_combine", U, ptr(U), ptr(x2), ptr(sent), ptr(dv), ptr(ds), B, T, d)       # U is v * s from here on
+            if ctx.needs_input_grad[0] and not in_sink:
+                dx = dv.view(B, T, d)
+            if ctx.needs_input_grad[1]:
+                dsent = torch.addmm(ds, dcs, Wbd)
+            if ctx.needs_input_grad[2] or ctx.needs_input_grad[4]:
+                dW = torch.empty(2, Hm, 4 * d, device=y.device, dtype=torch.float32)                       # [start ; end], full width
+                dW2 = dW.view(J, 4 * d)
+                _dw_f32s(dy2, x2, out=dW2[:, :d])                                                          # dW_a = dy^T v
+                _dw_f32s(dy2, U, out=dW2[:, 2 * d:3 * d])                                                  # dW_c = dy^T (v * s)
+                dW2[:, d:2 * d] = dcs.t() @ sent                                                           # dW_b
+                torch.add(dW2[:, :d], dW2[:, d:2 * d], out=dW2[:, 3 * d:])                                 # dW_d = dW_a + dW_b
+                dWs, dWe = dW[0], dW[1]
+        db1, dw2, db2 = db1p.sum(0), dw2p.sum(0), db2p.sum(0)
+        s2s, s2e = ctx.shapes
+        return (dx, dsent, dWs, db1[:Hm], dWe, db1[Hm:], dw2[:Hm].view(s2s), db2[0:1], dw2[Hm:].view(s2e), db2[1:2], dgate, None, None)
+
+
+def boundary_head_tall_params(x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate=None, mask=None):
+    """Boundary head on TALL's fusion from its parameters (tsg_boundary_head_tall_gemm; see _BoundaryHeadTall)."""
+    return _BoundaryHeadTall.apply(x, sent, Ws, bs, We, be, w2s, b2s, w2e, b2e, gate, mask, _sink_for(x))
 
 
 def boundary_head_gemm(x, w_start, w_end, cs, b1, w2, b2, gate=None, mask=None):

@@ -22,14 +22,16 @@ class Baseline(nn.Module):
         self.CMI = CrossModalInteraction.select_CMI(grounding_set['cross_name'], logger)(self.visual_dim, self.textual_dim)
         self.cross_dim = self.CMI.cross_dim()
         self.span_predictor = SpanPredictor.SpanPredictor_Boundary(self.cross_dim, grounding_set, drop_out=drop_out, logger=logger)
-        self._fused_head = isinstance(self.CMI, CrossModalInteraction.VideoSentenceConcat)
+        # the boundary head consumes (video, sent) without the CMI's tensor: 'vs' with either predictor, 'tall' and 'onlyvideo' with the MLP one
+        self._fused_head = (isinstance(self.CMI, CrossModalInteraction.VideoSentenceConcat)
+                            or isinstance(self.span_predictor.predictor, SpanPredictor.MLP_predictor))
 
     def forward(self, video_feat, query_feat, video_mask=None, query_mask=None):
         word_feature, sent_embed = self.sentence_encoder(query_feat)
         frame_feature = self.video_encoder(video_feat, word_feature)
         mask = video_mask if self.video_if_mask else None
-        if self._fused_head:        # [video_t | sent] is consumed without being materialised
-            start_prob, end_prob = self.span_predictor.forward_split(frame_feature, sent_embed, None, mask)
+        if self._fused_head:        # the fused feature is consumed without being materialised
+            start_prob, end_prob = self.span_predictor.forward_cmi(self.CMI, frame_feature, word_feature, sent_embed, None, mask)
         else:
             start_prob, end_prob = self.span_predictor(self.CMI(frame_feature, word_feature, sent_embed), v_mask=mask)
         return {'start': start_prob, 'end': end_prob}

@@ -35,12 +35,14 @@ class GMD(nn.Module):
 
         tod = TemporalOrderDiscriminator.select_temporal_order_discriminator('moment_pooling', logger)
         self.tod = tod(self.visual_dim, logger)
-        self._fused_head = isinstance(self.CMI, CrossModalInteraction.VideoSentenceConcat)
+        # the boundary head consumes (video, sent) without the CMI's tensor: 'vs' with either predictor, 'tall' and 'onlyvideo' with the MLP one
+        self._fused_head = (isinstance(self.CMI, CrossModalInteraction.VideoSentenceConcat)
+                            or isinstance(self.span_predictor.predictor, SpanPredictor.MLP_predictor))
 
     def _span(self, frame_feat, word_feat, sent_embed, gate, video_mask):
         mask = video_mask if self.video_if_mask else None
         if self._fused_head:
-            s, e = self.span_predictor.forward_split(frame_feat, sent_embed, gate, mask)
+            s, e = self.span_predictor.forward_cmi(self.CMI, frame_feat, word_feat, sent_embed, gate, mask)
         else:
             s, e = self.span_predictor(gate.unsqueeze(dim=2) * self.CMI(frame_feat, word_feat, sent_embed), v_mask=mask)
         return {'start': s, 'end': e}

@@ -1,7 +1,8 @@
 """Cross-modal fusion selectors (reference components/CrossModalInteraction.py).  The live choice
 'vs' (``VideoSentenceConcat``) builds ``[video_t | sent]``; the models do not call it on the fast
 path -- the boundary head consumes (video, sent) separately (kernel K3) -- but the module still
-returns the concatenated tensor when used standalone."""
+returns the concatenated tensor when used standalone.  The same holds for 'c' (``TALL``) and 'a' (``OnlyVideo``) with the MLP
+predictor: ``SpanPredictor_Boundary.forward_cmi`` takes the fused form of the module's ``kind``."""
 import torch
 import torch.nn as nn
 
@@ -19,6 +20,8 @@ def select_CMI(name, logger):
 
 
 class _CMI(nn.Module):
+    kind = None            # 'video' | 'vs' | 'tall': which fused form of the boundary head consumes (video, sent) without this module's output
+
     def __init__(self, video_dim, sent_dim, cross_dim):
         super().__init__()
         self.video_dim, self.sent_dim, self._cross_dim = video_dim, sent_dim, cross_dim
@@ -28,6 +31,8 @@ class _CMI(nn.Module):
 
 
 class OnlyVideo(_CMI):
+    kind = 'video'
+
     def __init__(self, video_dim, sent_dim, *args):
         super().__init__(video_dim, sent_dim, video_dim)
 
@@ -36,6 +41,8 @@ class OnlyVideo(_CMI):
 
 
 class VideoSentenceConcat(_CMI):
+    kind = 'vs'
+
     def __init__(self, video_dim, sent_dim, *args):
         super().__init__(video_dim, sent_dim, video_dim + sent_dim)
 
@@ -44,6 +51,8 @@ class VideoSentenceConcat(_CMI):
 
 
 class TALL(_CMI):
+    kind = 'tall'
+
     def __init__(self, video_dim, sent_dim, *args):
         assert video_dim == sent_dim
         super().__init__(video_dim, sent_dim, video_dim * 4)

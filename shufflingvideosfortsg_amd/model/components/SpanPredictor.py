@@ -42,6 +42,21 @@ class SpanPredictor_Boundary(nn.Module):
         return self.predictor(x, v_mask)
 
 
+    def forward_cmi(self, cmi, video_feat, word_feat, sent_feat, gate=None, v_mask=None):
+        """Same result as ``forward(gate * cmi(video, word, sent), v_mask)``; with the MLP predictor the fused form of ``cmi.kind`` runs where
+        its shapes and the precision mode allow it, and ``cmi`` itself is not called."""
+        if cmi.kind == 'vs':
+            return self.forward_split(video_feat, sent_feat, gate, v_mask)
+        if isinstance(self.predictor, MLP_predictor):
+            fused = self.predictor.forward_fused(cmi.kind, video_feat, sent_feat, gate, v_mask)
+            if fused is not None:
+                return fused
+        x = cmi(video_feat, word_feat, sent_feat)
+        if gate is not None:
+            x = gate.unsqueeze(2) * x
+        return self.predictor(x, v_mask)
+
+
 class MLP_predictor(nn.Module):
     """Two heads ``Linear(D,Hm) -> tanh -> Linear(Hm,1)``, optional mask_logits, softmax over T
     (reference SpanPredictor.py:60-85).  Everything after the first GEMM is one fused kernel."""
@@ -84,6 +99,36 @@ class MLP_predictor(nn.Module):
         y = TF.linear(video_feat, W1[:, :Dv])
         cs = TF.linear(sent_feat, W1[:, Dv:])
         return TF.boundary_score(y, cs, b1, w2, b2, gate, v_mask)
+
+
+    def fused_form(self, kind, B, T, Dv, Ds):
+        """Which fused head takes (CMI kind, shapes) in the current precision mode: 'vs' / 'tall' / 'video', or None (the concat + GEMM path)."""
+        Hm = self.hidden_dim
+        if kind == 'vs' and Dv + Ds == self.input_dim and TF.head_gemm_ok(B * T, 2 * Hm, Dv, T, Hm):
+            return 'vs'
+        if kind == 'tall' and 4 * Dv == self.input_dim and TF.tall_head_ok(B, T, Dv, Ds, Hm):
+            return 'tall'
+        if kind == 'video' and Dv == self.input_dim and TF.head_gemm_ok(B * T, 2 * Hm, Dv, T, Hm):
+            return 'video'
+        return None
+
+    def forward_fused(self, kind, video_feat, sent_feat, gate=None, v_mask=None):
+        """The boundary head on the CMI of ``kind`` without its output tensor ('tall': tsg_boundary_head_tall_gemm, 'video':
+        tsg_boundary_head_gemm with a zero sentence row, 'vs': ``forward_split``); None when no fused form takes the call (CPU tensors, bf16
+        storage, strict fp32, shapes outside the kernels' tiles): the caller keeps the concat path."""
+        if kind == 'vs':
+            return self.forward_split(video_feat, sent_feat, gate, v_mask)
+        if not (video_feat.is_cuda and video_feat.dtype == torch.float32 and video_feat.dim() == 3 and not TF.bf16_storage()):
+            return None
+        B, T, Dv = video_feat.shape
+        form = self.fused_form(kind, B, T, Dv, sent_feat.size(-1))
+        p = (self.start_mlp_1.weight, self.start_mlp_1.bias, self.end_mlp_1.weight, self.end_mlp_1.bias, self.start_mlp_2.weight,
+             self.start_mlp_2.bias, self.end_mlp_2.weight, self.end_mlp_2.bias)
+        if form == 'tall':
+            return TF.boundary_head_tall_params(video_feat, sent_feat, *p, gate, v_mask)
+        if form == 'video':
+            return TF.boundary_head_video_params(video_feat, *p, gate, v_mask)
+        return None
 
 
 class Self_Attention_predictor(nn.Module):
