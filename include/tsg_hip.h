@@ -233,16 +233,34 @@ int tsg_mha_bwd_rng(const void* Q, const void* K, const void* V, const void* O, 
  * tsg_lstm_fwd runs the T sequential steps (one launch per step covering both directions):
  *   Whh [2,4h,h];  out [T,B,2h] (forward half | reverse half);  saved for backward: R [T,2,B,h,4]
  *   (activated gates) and Cs [T,2,B,h] (cell states).  Limits: h % 4 == 0.
- * sync_ws: caller-owned workspace of TSG_LSTM_SYNC_BYTES bytes (may be NULL).  When given, T >= 8 (TSG_LSTM_PERSIST=0/1 in the
- *   environment or tsg_lstm_set_persist: never / always), h % 32 == 0 and h <= 512, ONE persistent launch runs all T steps (W_hh stationary in
- *   registers; workgroups hand h_t over by polling the sentinel-marked `out` slab itself); when the B rows need more workgroups
- *   than can be co-resident (one per CU: B > 128 at h = 512 on 256 CUs) the rows -- independent sequences -- are processed as
- *   consecutive persistent launches over balanced chunks of whole 16-row slices (B = 256 -> 2 x 128), never as step launches;
+ * sync_ws: caller-owned workspace of TSG_LSTM_SYNC_BYTES bytes (may be NULL).  With it ONE persistent launch can run all T steps (W_hh
+ *   stationary in registers; workgroups hand h_t over by polling the sentinel-marked `out` slab itself) -- when: "BiLSTM host dispatch" below;
  *   word 0 of sync_ws is non-zero afterwards if a bounded wait expired (results then invalid).  Otherwise one launch per time step.
- * dtype TSG_BF16 (persistent path only: sync_ws given, T > 1, h in {128, 256, 384, 512}; TSG_E_SHAPE otherwise): Gx, out and R are
+ * dtype TSG_BF16 (persistent path only; TSG_E_SHAPE otherwise): Gx, out and R are
  *   bf16 (R: four bf16 per unit), Cs / bias / Whh stay fp32; W_hh is rounded to bf16 once in the kernel's prologue, each step is
  *   ONE bf16 MFMA per k block, and h_t is exchanged -- and fed back -- as the bf16 value stored to `out` (16-bit sentinels).
- *   tsg_lstm_bwd_ws[_layout] with TSG_BF16: R, dOut and dG bf16; Cs, dHn, dbias and the ring workspace fp32.               */
+ *   tsg_lstm_bwd_ws[_layout] with TSG_BF16: R, dOut and dG bf16; Cs, dHn, dbias and the ring workspace fp32.
+ *
+ * BiLSTM HOST DISPATCH (csrc/lstm.hip: lstm_fwd_plan, lstm_bwd_plan -- each decision is made there once; tests/test_lstm_dispatch_gpu.py
+ * holds a case on either side of every boundary).  Every entry point first checks its arguments in one order: bias alignment, each
+ * pointer's NULL / 16-byte alignment in argument order, workspace alignment, dtype, positive dimensions, h % 4 == 0.
+ *   Forward.  PERSISTENT when a workspace is given, T > 1, h % 32 == 0, h <= 512 and the persist switch allows it (tsg_lstm_set_persist /
+ *   TSG_LSTM_PERSIST: 0 never, 1 always, -1 = default: T >= 8).  TSG_BF16 exists in the persistent kernels only: it IGNORES the T >= 8 rule
+ *   (persistent at any T > 1 unless the switch is 0), needs h in {128, 256, 384, 512}, and every other case is TSG_E_SHAPE.  Otherwise
+ *   (and when not even one 16-row slice can be co-resident) the fp32-storage dtypes run one launch per time step.  Among the persistent kernels:
+ *     - the exchange RING is used when the workspace holds it (tsg_lstm_fwd_ws with ws_bytes >= tsg_lstm_fwd_ws_bytes > 0, i.e. h in
+ *       {128, 256, 384, 512}) and tsg_lstm_set_ring allows it (default: B >= 96, or TSG_BF16 at B <= 32); else the kernels poll `out`;
+ *     - 64-UNIT workgroups (h / 64 per direction and 16-row slice): TSG_BF16, h = 512, ring, T * B * 8h < 2^31 and tsg_lstm_set_wide
+ *       (default: B > 128);
+ *     - 16-UNIT workgroups (h / 16 per slice, two per CU): h = 512, B <= 32 (TSG_LSTM_NW=4 / 8 forces / forbids), TSG_F32S or TSG_BF16 with ring;
+ *     - else 32-unit workgroups (h / 32 per slice, one per CU); h not in {128, 256, 384, 512}: a generic kernel in the fp32 arithmetic.
+ *   When the B rows need more workgroups than can be co-resident (B > 128 at h = 512 with 32-unit workgroups on 256 CUs) the rows --
+ *   independent sequences -- run as consecutive persistent launches over balanced chunks of whole 16-row slices (B = 256 -> 2 x 128), never as
+ *   step launches.  Ring or polling `out`, 64- or 32-unit workgroups, one launch or several: the same out / R / Cs bit for bit.
+ *   Backward (tsg_lstm_bwd_ws[_layout]).  PERSISTENT when ws is non-NULL, 16-byte aligned and of ws_bytes >= tsg_lstm_bwd_ws_bytes > 0
+ *   (h in {128, 256, 384, 512}), T > 1 and the persist switch allows it, with the same TSG_BF16 exception to T >= 8; h / 32 workgroups per
+ *   direction and 16-row slice, row chunks as in the forward (dbias accumulates over the chunks).  Otherwise the step kernels of
+ *   tsg_lstm_bwd (errors are then reported under that name); TSG_BF16 has none: TSG_E_SHAPE, reported before the pointers are checked.   */
 int tsg_lstm_fwd(const void* Gx, const void* Whh, void* out, void* R, void* Cs, void* sync_ws,
                  int B, int T, int h, int dtype, void* stream);
 /* Same, with the bias b_ih + b_hh [2,4h] added inside the kernel (bias may be NULL): for callers whose input GEMM has
@@ -255,14 +273,14 @@ int tsg_lstm_fwd_bias(const void* Gx, const void* bias, const void* Whh, void* o
  * h % 128 != 0 or h > 512), 16-byte aligned, caller-owned, contents irrelevant on entry.  With it the workgroups hand h_t over through
  * the ring (which stays inside the L2s it is exchanged through; in the TSG_F32S arithmetic it carries h already split into bf16 hi / lo
  * halves) instead of polling `out`; `out` is written with ordinary stores.  Results are bit-identical to tsg_lstm_fwd_bias.  A smaller
- * workspace (>= TSG_LSTM_SYNC_BYTES), or a shape at which the ring is not the faster path (tsg_lstm_set_ring), selects the
- * tsg_lstm_fwd_bias behaviour.                                                                                                         */
+ * workspace (>= TSG_LSTM_SYNC_BYTES; less is TSG_E_SHAPE), or a shape at which the ring is not the faster path ("BiLSTM host dispatch"
+ * above), selects the tsg_lstm_fwd_bias behaviour.                                                                                     */
 long long tsg_lstm_fwd_ws_bytes(int B, int T, int h);
 /* When tsg_lstm_fwd_ws takes the ring: -1 = automatic (default: where it measured faster -- B >= 96 rows, or TSG_BF16 at B <= 32; TSG_LSTM_XR=0/1
  * in the environment overrides the default), 0 = never, 1 = whenever the workspace holds one.  Process-wide, like tsg_lstm_set_persist. */
 int tsg_lstm_set_ring(int mode);
 /* With TSG_BF16 at h = 512 and a ring workspace, tsg_lstm_fwd_ws can run 64-UNIT workgroups (two A-tiles of W_hh per wave, 8 workgroups per
- * exchange group) on half the CUs: half the slab readers per L2 for twice the MFMA work per wave.  -1 = automatic (default: B >= 96 rows;
+ * exchange group) on half the CUs: half the slab readers per L2 for twice the MFMA work per wave.  -1 = automatic (default: B > 128 rows;
  * TSG_LSTM_W64=0/1 in the environment sets the initial mode), 0 = never, 1 = whenever the shape allows.  Same results bit for bit.           */
 int tsg_lstm_set_wide(int mode);
 int tsg_lstm_fwd_ws(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* ws, long long ws_bytes,
@@ -301,13 +319,14 @@ int tsg_lstm_bwd(const void* WhhT, const void* R, const void* Cs, const void* dO
 
 /* Same result through the persistent backward kernel when the caller provides its ring workspace: ws of at least
  * tsg_lstm_bwd_ws_bytes(B,T,h) bytes (0 = not available for this shape: h % 128 != 0 or h > 512), 16-byte aligned,
- * contents irrelevant.  One launch runs all T steps: workgroups exchange partial dh tiles through a 4-slot ring of
- * sentinel-marked, write-through 128-byte lines (no atomics or fences per step).  Falls back to tsg_lstm_bwd when ws is
- * NULL / too small or T < 8 (TSG_LSTM_PERSIST=0/1 or tsg_lstm_set_persist: never / always); rows beyond the co-resident
- * grid are processed in chunks as in the forward.                                                                   */
+ * contents irrelevant.  One launch runs all T steps: workgroups exchange partial dh tiles through a 2-slot ring of whole
+ * 128-byte lines whose values carry a GENERATION TAG in their lowest mantissa bit (no sentinels to re-mark, no atomics or fences
+ * per step).  When it runs, and when tsg_lstm_bwd's step kernels run instead: "BiLSTM host dispatch" above.             */
 long long tsg_lstm_bwd_ws_bytes(int B, int T, int h);
-/* 1 when tsg_lstm_bwd_ws will take the persistent path for this shape and workspace size (then, and only then, it also
- * fills dbias [2,4h] = d(b_ih + b_hh), the sum of dG over time and batch, when dbias is non-NULL).                  */
+/* 1 when tsg_lstm_bwd_ws will take the persistent path for this shape and workspace size (given a 16-byte aligned ws), answered by the
+ * plan the launch itself uses; the persistent path, and only it, also fills dbias [2,4h] = d(b_ih + b_hh), the sum of dG over time and
+ * batch.  The function has no dtype argument and answers for TSG_F32 / TSG_F32S: it follows the T >= 8 rule, so it returns 0 for
+ * 2 <= T < 8 although a TSG_BF16 layer of that length runs persistently (and fills dbias) all the same.                            */
 int tsg_lstm_bwd_ws_persistent(int B, int T, int h, long long ws_bytes);
 int tsg_lstm_bwd_ws(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
                     void* dG, void* dC_ws, void* ws, long long ws_bytes, void* dbias, int B, int T, int h, int dtype,

@@ -1118,15 +1118,6 @@ __global__ __launch_bounds__(512) void lstm_fwd_persist_w64_kernel(
   }
 }
 
-
-static int lstm_check(const char* fn, int B, int T, int h, int dtype) {
-  if (dtype != TSG_F32 && dtype != TSG_F32S && dtype != TSG_BF16)
-    return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S or TSG_BF16)", fn, dtype);
-  if (B <= 0 || T <= 0 || h <= 0) return set_error(TSG_E_SHAPE, "%s: non-positive dimension B=%d T=%d h=%d", fn, B, T, h);
-  if (h % 4) return set_error(TSG_E_ALIGN, "%s: hidden size %d must be a multiple of 4", fn, h);
-  return 0;
-}
-
 // ---------------------------------------------------------------------------------------------
 // backward, PERSISTENT (the default when the caller provides the ring workspace): exchange dh, not dG.
 // (A first version mirrored the forward literally -- consumers polling the sentinel-marked 4h-wide dG slab, 128 KiB per
@@ -1479,61 +1470,92 @@ __global__ __launch_bounds__(kThreads) void lstm_bwd_persist2_kernel(
 }  // namespace
 }  // namespace tsg
 
+// ---- host-side dispatch: the process switches, the argument check, the forward and backward plans, the chunked launches, the C entry
+// points (include/tsg_hip.h, "BiLSTM host dispatch", states the two plans for callers) ----
 #include <atomic>
-#include <mutex>
+#include <climits>
 using namespace tsg;
 
-// TSG_LSTM_PERSIST: unset = auto (persistent launch for sequences of >= 8 steps: 8.2 vs 17.3 us/step at
-// [B=128,T=128,h=512], 7.4 vs 11.3 us/step at [64,20,512]), 0 = never, 1 = whenever the grid fits.
-static std::atomic<int> g_persist{-2};   // -2: not decided yet (TSG_LSTM_PERSIST); tsg_lstm_set_persist overrides
-static int persist_mode() {
-  int v = g_persist.load(std::memory_order_relaxed);
-  if (v == -2) { const char* e = getenv("TSG_LSTM_PERSIST"); v = e ? atoi(e) : -1; g_persist.store(v, std::memory_order_relaxed); }
+// The process switches: every TSG_LSTM_* environment variable is read here, through env_int.
+constexpr int kUnset = INT_MIN;                  // env_int's answer for a variable that is not set, where no default can stand in for it
+static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+// The four switches with a setter are atomics that start "not read yet" and take their value from the environment on first use:
+//   persist  TSG_LSTM_PERSIST / tsg_lstm_set_persist: -1 = auto (persistent launch for sequences of >= 8 steps: 8.2 vs 17.3 us/step at
+//            [B=128,T=128,h=512], 7.4 vs 11.3 us/step at [64,20,512]), 0 = never, > 0 = whenever the grid fits
+//   l2x      TSG_LSTM_L2X / tsg_lstm_set_l2_exchange: default on; 0 = always write-through exchange stores (A/B measurements)
+//   ring     TSG_LSTM_XR / tsg_lstm_set_ring: -1 auto, 0 never, 1 always (lstm_fwd_plan has the rule and its measurements)
+//   wide     TSG_LSTM_W64 / tsg_lstm_set_wide: the 64-unit workgroups (lstm_fwd_persist_w64_kernel), -1 auto, 0 never, 1 whenever possible
+constexpr int kUnread = -2;
+static std::atomic<int> g_persist{kUnread}, g_l2x{kUnread}, g_ring{kUnread}, g_wide{kUnread};
+template <class Read> static int switch_value(std::atomic<int>& s, Read read) {
+  int v = s.load(std::memory_order_relaxed);
+  if (v == kUnread) s.store(v = read(), std::memory_order_relaxed);
   return v;
 }
+static int auto_or_flag(const char* name) { const int e = env_int(name, kUnset); return e == kUnset ? -1 : (e != 0); }
+static int persist_mode() { return switch_value(g_persist, [] { const int e = env_int("TSG_LSTM_PERSIST", -1); return e < 0 ? -1 : e; }); }
+static int l2_exchange() { return switch_value(g_l2x, [] { return env_int("TSG_LSTM_L2X", 1) != 0; }); }
+static int ring_mode() { return switch_value(g_ring, [] { return auto_or_flag("TSG_LSTM_XR"); }); }
+static int wide_mode() { return switch_value(g_wide, [] { return auto_or_flag("TSG_LSTM_W64"); }); }
 extern "C" int tsg_lstm_set_persist(int mode) { g_persist.store(mode < 0 ? -1 : (mode != 0), std::memory_order_relaxed); return 0; }
-static std::atomic<int> g_l2x{-1};   // -1: not decided yet (TSG_LSTM_L2X, default on); tsg_lstm_set_l2_exchange overrides
-static int l2_exchange() {        // TSG_LSTM_L2X=0: always write-through exchange stores (A/B measurements)
-  int v = g_l2x.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("TSG_LSTM_L2X"); v = e ? (atoi(e) != 0) : 1; g_l2x.store(v, std::memory_order_relaxed); }
-  return v;
-}
 extern "C" int tsg_lstm_set_l2_exchange(int on) { g_l2x.store(on != 0, std::memory_order_relaxed); return 0; }
+extern "C" int tsg_lstm_set_ring(int mode) { g_ring.store(mode < 0 ? -1 : (mode != 0), std::memory_order_relaxed); return 0; }
+extern "C" int tsg_lstm_set_wide(int mode) { g_wide.store(mode < 0 ? -1 : (mode != 0), std::memory_order_relaxed); return 0; }
+static bool persist_wanted(int T) { const int m = persist_mode(); return m > 0 || (m < 0 && T >= 8); }
 
-// Workgroups of a persistent kernel that can be co-resident: ONE per CU is counted (margin against over-reporting), cached
+// The three without a setter are read once (function-local statics: thread-safe).
+// TSG_LSTM_NW=4 / 8 forces the 16- / the 32-unit forward workgroups (anything else that is set: 8); 0 = by the rule of lstm_fwd_plan
+static int forced_nw() { static const int v = env_int("TSG_LSTM_NW", kUnset); return v == kUnset ? 0 : (v == 4 ? 4 : 8); }
+static bool pad_grids() { static const bool v = env_int("TSG_LSTM_PAD", 1) != 0; return v; }       // TSG_LSTM_PAD=0: natural grids (A/B; persist_grid)
+// launch flag bit 3: two-slot partial-dh ring in the backward (default; TSG_LSTM_RING=4 = the four slots of rounds 1-3, A/B).  Four slots of 8.4 MB are
+// 33.5 MB -- more than the eight 4 MB L2s together -- so the ring fell out of the L2s it is exchanged through: 1.0 GB of re-fetches per
+// launch at [128, 128, 512] (PMC: 1502 -> 454 MB read), 4.49 -> 3.88 us per step (f32s), 4.05 -> 3.27 (bf16 storage)
+static int ring2_flag() { static const int v = env_int("TSG_LSTM_RING", 2) == 4 ? 0 : 8; return v; }
+// bit 0: L2-local exchange allowed; bit 1: inject a start-barrier timeout (TSG_LSTM_INJECT_TIMEOUT, read on EVERY launch: the tests flip it in one process)
+static int launch_flags() { return (l2_exchange() ? 1 : 0) | (env_int("TSG_LSTM_INJECT_TIMEOUT", 0) != 0 ? 2 : 0) | ring2_flag(); }
+
+// The argument check of every entry point: bias alignment, then each pointer's NULL / alignment in the order given, the workspace's
+// alignment, the dtype, the dimensions, h % 4 -- the first failure is reported under the entry point's name `fn`.
+static int lstm_check_args(const char* fn, std::initializer_list<const void*> ptrs, const void* bias, const void* ws, int B, int T, int h, int dtype) {
+  if (bias && !aligned16(bias)) return set_error(TSG_E_ALIGN, "%s: bias %p is not 16-byte aligned", fn, bias);
+  for (const void* p : ptrs) {
+    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
+    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
+  }
+  if (ws && !aligned16(ws)) return set_error(TSG_E_ALIGN, "%s: workspace %p is not 16-byte aligned", fn, ws);
+  if (dtype != TSG_F32 && dtype != TSG_F32S && dtype != TSG_BF16)
+    return set_error(TSG_E_DTYPE, "%s: dtype %d not supported (TSG_F32, TSG_F32S or TSG_BF16)", fn, dtype);
+  if (B <= 0 || T <= 0 || h <= 0) return set_error(TSG_E_SHAPE, "%s: non-positive dimension B=%d T=%d h=%d", fn, B, T, h);
+  if (h % 4) return set_error(TSG_E_ALIGN, "%s: hidden size %d must be a multiple of 4", fn, h);
+  return 0;
+}
+
+// Workgroups of a persistent kernel that can be co-resident: `per_cu` per CU are counted (margin against over-reporting), cached
 // per (device, kernel INSTANTIATION) -- the instantiations differ in LDS and register footprint, so an occupancy answer is never shared
-// between them (a slot number used to stand for several kernels).  0 = the kernel cannot run persistently here.
-// (`slot` is the callers' old cache index: unused.)
+// between them.  0 = the kernel cannot run persistently here.
 template <class K>
-static int persist_capacity(int /*slot*/, K kern, int threads, size_t lds, int per_cu) {
+static int persist_capacity(K kern, int threads, size_t lds, int per_cu) {
   static std::mutex mu;
   static std::map<std::pair<int, const void*>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0) return 0;
   // the LDS attribute is per (device, instantiation): requested on every call (a table hit after the first)
-  hipError_t e1 = allow_lds(kern, lds);
-  if (e1 != hipSuccess) return 0;
+  if (allow_lds(kern, lds) != hipSuccess) return 0;
   const auto key = std::make_pair(dev, reinterpret_cast<const void*>(kern));
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-  }
-  int cus = 0, per = 0;
-  e1 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e1 == hipSuccess) e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, threads, lds);
-  const int cap = (e1 == hipSuccess && per >= per_cu) ? cus * per_cu : 0;
   std::lock_guard<std::mutex> lock(mu);
-  cache[key] = cap;
-  return cap;
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  int cus = 0, per = 0;
+  hipError_t e1 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (e1 == hipSuccess) e1 = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, threads, lds);
+  return cache[key] = (e1 == hipSuccess && per >= per_cu) ? cus * per_cu : 0;
 }
 // Rows per launch when the B rows of a layer need more workgroups than fit: balanced chunks of whole 16-row slices, each
 // with 2 * wgs_per_slice * slices <= cap workgroups.  0 = not even one slice fits.
 static int persist_chunk_rows(int B, int wgs_per_slice, int cap) {
   const int max_slices = cap / (2 * wgs_per_slice);
   if (max_slices <= 0) return 0;
-  const int slices = cdiv(B, 16);
-  const int chunks = cdiv(slices, max_slices);
+  const int slices = cdiv(B, 16), chunks = cdiv(slices, max_slices);
   return cdiv(slices, chunks) * 16;
 }
 // Grid of a persistent launch with `slices` 16-row batch slices: 2 * slices exchange groups of `wgs` workgroups each.  Workgroup i
@@ -1547,173 +1569,146 @@ static int persist_chunk_rows(int B, int wgs_per_slice, int cap) {
 // grid): packing them two per XCD on six XCDs measured 4.68 -> 4.15 us in f32s but 3.53 -> 3.75 in bf16.
 // TSG_LSTM_PAD=0: natural grids (A/B).  Correctness never depends on the placement: the groups verify it (grid_start).
 static int persist_grid(int slices, int wgs, int cap) {
-  static const bool pad = !(getenv("TSG_LSTM_PAD") && atoi(getenv("TSG_LSTM_PAD")) == 0);
   const int natural = 2 * slices * wgs, padded = 8 * wgs;
-  return (pad && 2 * slices < 8 && padded <= cap) ? padded : natural;
+  return (pad_grids() && 2 * slices < 8 && padded <= cap) ? padded : natural;
 }
-static int launch_flags() {       // bit 0: L2-local exchange allowed; bit 1: inject a start-barrier timeout (tests)
-  const char* e = getenv("TSG_LSTM_INJECT_TIMEOUT");
-  // bit 3: two-slot partial-dh ring in the backward (default; TSG_LSTM_RING=4 = the four slots of rounds 1-3, A/B).  Four slots of 8.4 MB are
-  // 33.5 MB -- more than the eight 4 MB L2s together -- so the ring fell out of the L2s it is exchanged through: 1.0 GB of re-fetches per
-  // launch at [128, 128, 512] (PMC: 1502 -> 454 MB read), 4.49 -> 3.88 us per step (f32s), 4.05 -> 3.27 (bf16 storage)
-  static const int ring2 = [] { const char* r = getenv("TSG_LSTM_RING"); return (r && atoi(r) == 4) ? 0 : 8; }();
-  return (l2_exchange() ? 1 : 0) | ((e && atoi(e) != 0) ? 2 : 0) | ring2;
-}
-static bool persist_wanted(int T) { const int m = persist_mode(); return m > 0 || (m < 0 && T >= 8); }
-
-static int lstm_fwd_impl(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* sync_ws, long long ws_bytes,
-                         int B, int T, int h, int dtype, int batch_major, void* stream);
-
-extern "C" int tsg_lstm_fwd(const void* Gx, const void* Whh, void* out, void* R, void* Cs, void* sync_ws,
-                            int B, int T, int h, int dtype, void* stream) {
-  return lstm_fwd_impl(Gx, nullptr, Whh, out, R, Cs, sync_ws, sync_ws ? kSyncBytes : 0, B, T, h, dtype, 0, stream);
+// More rows than co-resident workgroups allow (B = 256 at h = 512: grid 512 on 256 CUs): the rows are independent, so a persistent layer
+// runs as consecutive launches over balanced row chunks (pointer offsets; the kernels' Bs = B keeps the tensors' strides).  Per chunk: zero(c0)
+// clears the sync words (one memset node), launch(grid, c0, Bc, seq) starts rows c0 .. c0 + Bc - 1; seq = their first sequence row in either layout.
+template <class Zero, class Launch>
+static int launch_row_chunks(const char* fn, int B, int T, int bm, int rows, int wgs, int cap, Zero zero, Launch launch) {
+  for (int c0 = 0; c0 < B; c0 += rows) {
+    const int Bc = B - c0 < rows ? B - c0 : rows;
+    const size_t seq = bm ? (size_t)c0 * T : (size_t)c0;
+    const hipError_t e = zero(c0);
+    if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
+    launch(persist_grid(cdiv(Bc, 16), wgs, cap), c0, Bc, seq);
+  }
+  return check_launch(fn);
 }
 
-extern "C" int tsg_lstm_fwd_bias(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* sync_ws,
-                                 int B, int T, int h, int dtype, int batch_major, void* stream) {
-  return lstm_fwd_impl(Gx, bias, Whh, out, R, Cs, sync_ws, sync_ws ? kSyncBytes : 0, B, T, h, dtype, batch_major, stream);
+// ---- forward: dynamic LDS of the persistent kernels, their launchers, the plan ----
+constexpr int kFwdHLS = kPersistMaxH + 8;        // slab row stride, fixed: the prefetch may read (never use) columns up to kPersistMaxH
+// slab, h tile, Gx / R / Cs tiles (fp32, 32 units: the largest)
+constexpr size_t kFwdPersistLds = sizeof(float) * ((size_t)kSlabFloats + 16 * 36 + 2 * 16 * 128 + 16 * (136 + 36) + 4);
+static_assert(kSlabFloats >= 16 * (kPersistMaxH + 8), "slab region holds the fp32 slab too");
+// lstm_fwd_persist_w64_kernel: slab, h tile [16][65], Gx / R / Cs tiles [16][4 * 32 + 4], [16][64 * 2 + 8], [16][64 + 4]
+constexpr size_t kFwdWideLds = sizeof(float) * ((size_t)kSlabFloats + 16 * 65 + 16 * (4 * 32 + 4) + 16 * (64 * 2 + 8) + 16 * (64 + 4) + 4);
+// One launcher signature for every persistent forward kernel: rows c0 .. c0 + Bc - 1 of the layer, seq = their first sequence row.
+typedef void (*FwdLaunch)(int grid, hipStream_t st, const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* ws,
+                          int Bc, int B, int T, int h, int bm, size_t seq, int c0);
+template <int HJ, int MODE, int NW, bool XR>
+static void launch_fwd_persist(int grid, hipStream_t st, const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs,
+                               void* ws, int Bc, int B, int T, int h, int bm, size_t seq, int c0) {
+  typedef typename SeqT<MODE>::type GT;
+  const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
+  hipLaunchKernelGGL((lstm_fwd_persist_kernel<HJ, MODE, NW, XR>), dim3(grid), dim3(64 * NW), kFwdPersistLds, st, (const GT*)Gx + seq * K8,
+                     (const float*)bias, (const float*)Whh, (GT*)out + seq * H2, (GT*)R + (size_t)c0 * h * 4, (float*)Cs + (size_t)c0 * h,
+                     (unsigned*)ws, Bc, B, T, h, kFwdHLS, launch_flags(), bm, error_sink(), XR ? (unsigned*)((char*)ws + kSyncBytes) : nullptr);
 }
-
+static void launch_fwd_wide(int grid, hipStream_t st, const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* ws,
+                            int Bc, int B, int T, int h, int bm, size_t seq, int c0) {
+  const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
+  hipLaunchKernelGGL(lstm_fwd_persist_w64_kernel<32>, dim3(grid), dim3(512), kFwdWideLds, st, (const lstm_bf16*)Gx + seq * K8, (const float*)bias,
+                     (const float*)Whh, (lstm_bf16*)out + seq * H2, (lstm_bf16*)R + (size_t)c0 * h * 4, (float*)Cs + (size_t)c0 * h, (unsigned*)ws,
+                     Bc, B, T, h, launch_flags(), bm, error_sink(), (unsigned*)((char*)ws + kSyncBytes));
+}
 // workspace of tsg_lstm_fwd_ws: the sync words + the exchange ring [4 slots][2 * ceil(B/16) groups][16 rows][h] dwords (0: no ring for this h)
 extern "C" long long tsg_lstm_fwd_ws_bytes(int B, int T, int h) {
   (void)T;
   if (B <= 0 || h <= 0 || h % 128 || h > kPersistMaxH) return 0;
   return kSyncBytes + 4LL * 2 * cdiv(B, 16) * 16 * h * (long long)sizeof(float);
 }
-
-extern "C" int tsg_lstm_fwd_ws(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* ws, long long ws_bytes,
-                               int B, int T, int h, int dtype, int batch_major, void* stream) {
-  if (ws && ws_bytes < kSyncBytes) return set_error(TSG_E_SHAPE, "tsg_lstm_fwd_ws: workspace of %lld bytes is smaller than TSG_LSTM_SYNC_BYTES", ws_bytes);
-  return lstm_fwd_impl(Gx, bias, Whh, out, R, Cs, ws, ws ? ws_bytes : 0, B, T, h, dtype, batch_major, stream);
-}
-
-// Where the ring pays (profiles/r5/lstm_fwd_ring_*_v1.txt, one MI355X, us per step out-polling -> ring): at the full-chip grids -- [128, 128, 512]
-// f32s 3.85-3.91 -> 3.81-3.83 batch-major, 3.76 -> 3.60 time-major; bf16 storage 3.75-3.77 -> 3.69-3.70 -- and, with bf16 storage, at the
-// 16-pair shards of BASELINE configs 3 / 4 (<= 32 rows), where it makes the 4-wave workgroups possible (one A-tile per wave needs no second
-// register set: 146 VGPRs): 3.26 -> 2.87 at [32, 512, 512], 3.16 -> 2.67 at [16, 128, 512].  It LOSES at half-chip grids ([64, ., 512]: 3.32 ->
-// 3.49 f32s: one group per XCD, nothing contends for the L2 and the extra re-mark / `out` stores are pure cost) and in f32s at <= 32 rows (the
-// 4-wave f32s ring kernel spills: 2.91 -> 3.32).  TSG_LSTM_XR=1 / 0: always / never (A/B).
-static std::atomic<int> g_xr{-2};     // -2: not decided yet (TSG_LSTM_XR); -1 auto, 0 never, 1 always; tsg_lstm_set_ring overrides
-static bool xr_wanted(int B, bool bf) {
-  int v = g_xr.load(std::memory_order_relaxed);
-  if (v == -2) { const char* e = getenv("TSG_LSTM_XR"); v = e ? (atoi(e) != 0) : -1; g_xr.store(v, std::memory_order_relaxed); }
-  if (v >= 0) return v != 0;
-  return B >= 96 || (bf && B <= 32);
-}
-extern "C" int tsg_lstm_set_ring(int mode) { g_xr.store(mode < 0 ? -1 : (mode != 0), std::memory_order_relaxed); return 0; }
-// 64-unit workgroups (lstm_fwd_persist_w64_kernel: bf16 storage, h = 512, ring workspace): -1 automatic (more than 128 rows: one launch where the
-// 32-unit kernel needs two), 0 never, 1 whenever possible
-static std::atomic<int> g_w64{-2};
-static bool w64_wanted(int B) {
-  int v = g_w64.load(std::memory_order_relaxed);
-  if (v == -2) { const char* e = getenv("TSG_LSTM_W64"); v = e ? (atoi(e) != 0) : -1; g_w64.store(v, std::memory_order_relaxed); }
-  return v >= 0 ? v != 0 : B > 128;      // (up to 128 rows the 32-unit kernel with staged streams is faster: 2.19 vs 2.6 us per step)
-}
-extern "C" int tsg_lstm_set_wide(int mode) { g_w64.store(mode < 0 ? -1 : (mode != 0), std::memory_order_relaxed); return 0; }
-
+struct FwdPlan {
+  enum Kind { Step, Persist, Wide } kind = Step;  // launch-per-step kernels; 32- / 16-unit persistent workgroups; 64-unit persistent workgroups
+  FwdLaunch go = nullptr;                         // persistent kinds: the kernel instantiation
+  int threads = 0; size_t lds = 0;                // per workgroup
+  int wgs = 0, per_cu = 1;                        // workgroups per (direction, 16-row slice); of them co-resident on a CU (the 16-unit kernel: 2)
+  int cap = 0, rows = 0;                          // co-resident workgroups on this device (persist_capacity), rows per launch (persist_chunk_rows)
+  bool ring = false;                              // h_t goes through the workspace's exchange ring, not through polling `out`
+};
+// the kernel table: (HJ = h / 16 or 0, MODE, NW, XR) -> launcher and co-residency
 template <int HJ, int MODE, int NW, bool XR>
-static void launch_fwd_persist(int grid, size_t lds, hipStream_t st, const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs,
-                               void* ws, int Bc, int B, int T, int h, int HLS, int bm, size_t seq, int c0) {
-  typedef typename SeqT<MODE>::type GT;
-  const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
-  hipLaunchKernelGGL((lstm_fwd_persist_kernel<HJ, MODE, NW, XR>), dim3(grid), dim3(64 * NW), lds, st, (const GT*)Gx + seq * K8, (const float*)bias,
-                     (const float*)Whh, (GT*)out + seq * H2, (GT*)R + (size_t)c0 * h * 4, (float*)Cs + (size_t)c0 * h, (unsigned*)ws, Bc, B, T, h,
-                     HLS, launch_flags(), bm, error_sink(), XR ? (unsigned*)((char*)ws + kSyncBytes) : nullptr);
+static void fwd_pick(FwdPlan& p, int h) {
+  p.kind = FwdPlan::Persist; p.go = launch_fwd_persist<HJ, MODE, NW, XR>; p.ring = XR;
+  p.threads = 64 * NW; p.lds = kFwdPersistLds; p.wgs = h / (4 * NW); p.per_cu = NW == 4 ? 2 : 1;
+  p.cap = persist_capacity(lstm_fwd_persist_kernel<HJ, MODE, NW, XR>, p.threads, p.lds, p.per_cu);
+}
+template <int MODE, bool XR>
+static void fwd_pick_h(FwdPlan& p, int h) {
+  if (h == 512) fwd_pick<32, MODE, 8, XR>(p, h); else if (h == 384) fwd_pick<24, MODE, 8, XR>(p, h);
+  else if (h == 256) fwd_pick<16, MODE, 8, XR>(p, h); else if (h == 128) fwd_pick<8, MODE, 8, XR>(p, h);
+  else fwd_pick<0, 0, 8, false>(p, h);            // other hidden sizes (multiples of 32): the generic fp32 kernel, polling `out`
+}
+
+// THE forward plan: which kernel runs a layer of B rows, T steps, h units in `dtype`, given a workspace of ws_bytes (has_ws: one was passed;
+// ws_bytes >= TSG_LSTM_SYNC_BYTES then).  Returns 0 and fills `p`, or the error of a TSG_BF16 layer that no persistent kernel takes.
+static int lstm_fwd_plan(const char* fn, int B, int T, int h, int dtype, bool has_ws, long long ws_bytes, FwdPlan& p) {
+  p = FwdPlan();
+  const bool bf = dtype == TSG_BF16, split = dtype == TSG_F32S;
+  // Persistent path (weights stationary, one launch for all T steps -- needs every workgroup resident): the caller gave the sync words; T > 1;
+  // the switch allows it -- automatically for T >= 8 (measurements: at g_persist), a rule that bf16 storage IGNORES: it exists in the persistent
+  // kernels only and runs there at any T > 1 unless the switch says never; h % 32 == 0 and h <= kPersistMaxH (whole 32-unit workgroups, the
+  // slab fits the LDS), in bf16 storage h % 128 == 0 (the kernels specialised for h: 128 / 256 / 384 / 512).
+  const bool wanted = bf ? persist_mode() != 0 : persist_wanted(T);
+  const bool persistent = has_ws && T > 1 && wanted && h % 32 == 0 && h <= kPersistMaxH && (!bf || h % 128 == 0);
+  // bf16 storage: other shapes are reported as unsupported and the caller runs them through the fp32-storage entry points
+  if (bf && !persistent)
+    return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs the persistent kernel (sync_ws given, TSG_LSTM_PERSIST != 0, T > 1, h in "
+                     "{128,256,384,512}); got T=%d h=%d", fn, T, h);
+  if (!persistent) return 0;                      // FwdPlan::Step
+  // the exchange ring (XR kernels, the 64-unit kernel): the caller's workspace holds it, hidden sizes 128 / 256 / 384 / 512
+  const long long need = tsg_lstm_fwd_ws_bytes(B, T, h);
+  const bool have_ring = need > 0 && ws_bytes >= need;
+  // 64-unit workgroups: bf16 storage at h = 512 with a ring, automatically for more than 128 rows -- one launch where the 32-unit kernel
+  // needs two, 8 workgroups per exchange group on half the CUs (see the kernel); up to 128 rows the 32-unit kernel with staged streams is
+  // faster: 2.19 vs 2.6 us per step.  The kernel indexes the sequence tensors with 32 bits: T * B * 8h < 2^31.
+  const int wm = wide_mode();
+  if (bf && h == 512 && have_ring && (wm >= 0 ? wm != 0 : B > 128) && (long long)T * B * 8 * h < (1LL << 31)) {
+    FwdPlan w;
+    w.kind = FwdPlan::Wide; w.go = launch_fwd_wide; w.ring = true; w.threads = 512; w.lds = kFwdWideLds; w.wgs = h / 64;
+    w.cap = persist_capacity(lstm_fwd_persist_w64_kernel<32>, w.threads, w.lds, w.per_cu);
+    w.rows = persist_chunk_rows(B, w.wgs, w.cap);
+    if (w.rows > 0) { p = w; return 0; }
+  }
+  // Where the ring pays (profiles/r5/lstm_fwd_ring_*_v1.txt, one MI355X, us per step out-polling -> ring): at the full-chip grids -- [128, 128, 512]
+  // f32s 3.85-3.91 -> 3.81-3.83 batch-major, 3.76 -> 3.60 time-major; bf16 storage 3.75-3.77 -> 3.69-3.70 -- and, with bf16 storage, at the
+  // 16-pair shards of BASELINE configs 3 / 4 (<= 32 rows), where it makes the 4-wave workgroups possible (one A-tile per wave needs no second
+  // register set: 146 VGPRs): 3.26 -> 2.87 at [32, 512, 512], 3.16 -> 2.67 at [16, 128, 512].  It LOSES at half-chip grids ([64, ., 512]: 3.32 ->
+  // 3.49 f32s: one group per XCD, nothing contends for the L2 and the extra re-mark / `out` stores are pure cost) and in f32s at <= 32 rows (the
+  // 4-wave f32s ring kernel spills: 2.91 -> 3.32).  TSG_LSTM_XR=1 / 0: always / never (A/B).
+  const int rm = ring_mode();
+  const bool xr = have_ring && (rm >= 0 ? rm != 0 : (B >= 96 || (bf && B <= 32)));
+  // 16-unit workgroups of 4 waves (half the MFMA and gate work per workgroup and step, twice the workgroups): slower when they
+  // have to share CUs (two per CU at 128 rows: 5.15 vs 4.59 us per step), faster when the chip is mostly idle -- up to 32 rows
+  // (the 16-pair per-GPU shards of BASELINE configs 3 / 4): 3.01 -> 2.82 us per step at [32, 512, 512], 2.85 -> 2.68 at 16 rows,
+  // no difference at 40 / 48 rows (profiles/r4/lstm_fwd_nw4_small_batch_ab_v1.txt).  TSG_LSTM_NW=4 / 8 forces one of them.  Only
+  // h = 512, in f32s or in bf16 storage through the ring, has the kernel.
+  const int nw = forced_nw();
+  const bool nw4 = (nw == 4 || (nw == 0 && B <= 32)) && h == 512 && (split || (bf && xr));
+  if (nw4 && bf) fwd_pick<32, 2, 4, true>(p, h);
+  else if (nw4) { if (xr) fwd_pick<32, 1, 4, true>(p, h); else fwd_pick<32, 1, 4, false>(p, h); }
+  else if (bf) { if (xr) fwd_pick_h<2, true>(p, h); else fwd_pick_h<2, false>(p, h); }
+  else if (split) { if (xr) fwd_pick_h<1, true>(p, h); else fwd_pick_h<1, false>(p, h); }   // (hidden sizes off the table: the fp32 arithmetic)
+  else { if (xr) fwd_pick_h<0, true>(p, h); else fwd_pick_h<0, false>(p, h); }
+  p.rows = persist_chunk_rows(B, p.wgs, p.cap);
+  if (p.rows > 0) return 0;
+  if (bf) return set_error(TSG_E_SHAPE, "%s: the persistent kernel cannot be co-resident on this device (TSG_BF16)", fn);
+  p = FwdPlan();                                  // not co-resident here: the step kernels
+  return 0;
 }
 
 static int lstm_fwd_impl(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* sync_ws, long long ws_bytes,
                          int B, int T, int h, int dtype, int batch_major, void* stream) {
   const int bm = batch_major != 0;
   const char* fn = "tsg_lstm_fwd";
-  if (bias && !aligned16(bias)) return set_error(TSG_E_ALIGN, "%s: bias %p is not 16-byte aligned", fn, bias);
-  for (const void* p : {Gx, Whh, (const void*)out, (const void*)R, (const void*)Cs}) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  if (sync_ws && !aligned16(sync_ws)) return set_error(TSG_E_ALIGN, "%s: workspace %p is not 16-byte aligned", fn, sync_ws);
-  int rc = lstm_check(fn, B, T, h, dtype);
-  if (rc) return rc;
+  FwdPlan p;
+  if (int rc = lstm_check_args(fn, {Gx, Whh, out, R, Cs}, bias, sync_ws, B, T, h, dtype)) return rc;
+  if (int rc = lstm_fwd_plan(fn, B, T, h, dtype, sync_ws != nullptr, ws_bytes, p)) return rc;
   auto st = static_cast<hipStream_t>(stream);
-  // persistent path: weights stationary, one launch for all T steps -- needs every workgroup resident
-  const bool bf = dtype == TSG_BF16;
-  // bf16 storage exists in the persistent kernels only (hidden sizes 128 / 256 / 384 / 512): other shapes are reported as
-  // unsupported and the caller runs them through the fp32-storage entry points
-  if (bf && !(sync_ws && persist_mode() != 0 && h % 128 == 0 && h <= kPersistMaxH && T > 1))
-    return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs the persistent kernel (sync_ws given, TSG_LSTM_PERSIST != 0, T > 1, h in "
-                     "{128,256,384,512}); got T=%d h=%d", fn, T, h);
-  if (sync_ws && (bf || persist_wanted(T)) && h % 32 == 0 && h <= kPersistMaxH && T > 1) {
-    // 16-unit workgroups of 4 waves (half the MFMA and gate work per workgroup and step, twice the workgroups): slower when they
-    // have to share CUs (two per CU at 128 rows: 5.15 vs 4.59 us per step), faster when the chip is mostly idle -- up to 32 rows
-    // (the 16-pair per-GPU shards of BASELINE configs 3 / 4): 3.01 -> 2.82 us per step at [32, 512, 512], 2.85 -> 2.68 at 16 rows,
-    // no difference at 40 / 48 rows (profiles/r4/lstm_fwd_nw4_small_batch_ab_v1.txt).  TSG_LSTM_NW=4 / 8 forces one of them.
-    static int nw_env = -1;
-    if (nw_env < 0) { const char* e = getenv("TSG_LSTM_NW"); nw_env = e ? (atoi(e) == 4 ? 4 : 8) : 0; }
-    const bool split = dtype == TSG_F32S;                  // other hidden sizes: the fp32 arithmetic (more accurate, slower)
-    // the exchange ring (XR kernels): the caller's workspace holds it, hidden sizes 128 / 256 / 384 / 512
-    const long long need = tsg_lstm_fwd_ws_bytes(B, T, h);
-    if (bf && h == 512 && need > 0 && ws_bytes >= need && w64_wanted(B) && (long long)T * B * 8 * h < (1LL << 31)) {
-      // bf16 storage at the full-chip sizes: 64-unit workgroups, 8 per exchange group, on half the CUs (see the kernel)
-      auto kw = lstm_fwd_persist_w64_kernel<32>;
-      const size_t wlds = sizeof(float) * ((size_t)kSlabFloats + 16 * 65 + 16 * (4 * 32 + 4) + 16 * (64 * 2 + 8) + 16 * (64 + 4) + 4);
-      const int capw = persist_capacity(3, kw, 512, wlds, 1);
-      const int rowsw = persist_chunk_rows(B, h / 64, capw);
-      if (rowsw > 0) {
-        const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
-        for (int c0 = 0; c0 < B; c0 += rowsw) {
-          const int Bc = B - c0 < rowsw ? B - c0 : rowsw;
-          const size_t seq = bm ? (size_t)c0 * T : (size_t)c0;
-          hipError_t e = zero_async(sync_ws, kSyncBytes, st);
-          if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
-          hipLaunchKernelGGL(kw, dim3(persist_grid(cdiv(Bc, 16), h / 64, capw)), dim3(512), wlds, st, (const lstm_bf16*)Gx + seq * K8, (const float*)bias,
-                             (const float*)Whh, (lstm_bf16*)out + seq * H2, (lstm_bf16*)R + (size_t)c0 * h * 4, (float*)Cs + (size_t)c0 * h,
-                             (unsigned*)sync_ws, Bc, B, T, h, launch_flags(), bm, error_sink(), (unsigned*)((char*)sync_ws + kSyncBytes));
-        }
-        return check_launch(fn);
-      }
-    }
-    const bool xr = need > 0 && ws_bytes >= need && xr_wanted(B, bf);
-    const int NW = ((nw_env == 4 || (nw_env == 0 && B <= 32)) && h == 512 && (split || (bf && xr))) ? 4 : 8;
-    const int HLS = kPersistMaxH + 8;                      // fixed: the prefetch above may read (never use) columns up to kPersistMaxH
-    const size_t plds = sizeof(float) * ((size_t)kSlabFloats + 16 * 36 + 2 * 16 * 128 + 16 * (136 + 36) + 4);     // slab, h tile, Gx / R / Cs tiles (fp32, 32 units: the largest)
-    static_assert(kSlabFloats >= 16 * (kPersistMaxH + 8), "slab region holds the fp32 slab too");
-    typedef void (*Launch)(int, size_t, hipStream_t, const void*, const void*, const void*, void*, void*, void*, void*, int, int, int, int, int, int, size_t, int);
-    Launch go = nullptr;
-    int cap = 0;
-#define TSG_FWD_PICK(HJ_, MODE_, NW_, XR_, SLOT_)                                                                          \
-    { go = launch_fwd_persist<HJ_, MODE_, NW_, XR_>;                                                                        \
-      cap = persist_capacity(SLOT_, lstm_fwd_persist_kernel<HJ_, MODE_, NW_, XR_>, 64 * NW_, plds, NW_ == 4 ? 2 : 1); }
-#define TSG_FWD_PICK_H(MODE_, XR_, SLOT_)                                                                                  \
-    { if (h == 512) TSG_FWD_PICK(32, MODE_, 8, XR_, SLOT_) else if (h == 384) TSG_FWD_PICK(24, MODE_, 8, XR_, SLOT_)        \
-      else if (h == 256) TSG_FWD_PICK(16, MODE_, 8, XR_, SLOT_) else if (h == 128) TSG_FWD_PICK(8, MODE_, 8, XR_, SLOT_) }
-    if (NW == 4) {
-      if (bf) TSG_FWD_PICK(32, 2, 4, true, 1)
-      else if (xr) TSG_FWD_PICK(32, 1, 4, true, 1)
-      else TSG_FWD_PICK(32, 1, 4, false, 1)
-    } else if (bf) {
-      if (xr) TSG_FWD_PICK_H(2, true, 3) else TSG_FWD_PICK_H(2, false, 3)
-    } else if (split) {
-      if (xr) TSG_FWD_PICK_H(1, true, 0) else TSG_FWD_PICK_H(1, false, 0)
-    } else {
-      if (xr) TSG_FWD_PICK_H(0, true, 0) else TSG_FWD_PICK_H(0, false, 0)
-    }
-    if (!go) TSG_FWD_PICK(0, 0, 8, false, 0)               // other hidden sizes (multiples of 32): the generic fp32 kernel, polling `out`
-#undef TSG_FWD_PICK_H
-#undef TSG_FWD_PICK
-    // more rows than co-resident workgroups allow (B = 256 at h = 512: grid 512 on 256 CUs): the rows are independent, so the
-    // layer runs as consecutive launches over balanced row chunks (pointer offsets; Bs = B keeps the tensors' strides)
-    const int rows = persist_chunk_rows(B, h / (4 * NW), cap);
-    if (bf && rows <= 0) return set_error(TSG_E_SHAPE, "%s: the persistent kernel cannot be co-resident on this device (TSG_BF16)", fn);
-    if (rows > 0) {
-      for (int c0 = 0; c0 < B; c0 += rows) {
-        const int Bc = B - c0 < rows ? B - c0 : rows;
-        const size_t seq = bm ? (size_t)c0 * T : (size_t)c0;              // first sequence row of the chunk
-        hipError_t e = zero_async(sync_ws, kSyncBytes, st);
-        if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
-        go(persist_grid(cdiv(Bc, 16), h / (4 * NW), cap), plds, st, Gx, bias, Whh, out, R, Cs, sync_ws, Bc, B, T, h, HLS, bm, seq, c0);
-      }
-      return check_launch(fn);
-    }
-  }
+  if (p.kind != FwdPlan::Step)
+    return launch_row_chunks(fn, B, T, bm, p.rows, p.wgs, p.cap, [&](int) { return zero_async(sync_ws, kSyncBytes, st); },
+                             [&](int grid, int c0, int Bc, size_t seq) { p.go(grid, st, Gx, bias, Whh, out, R, Cs, sync_ws, Bc, B, T, h, bm, seq, c0); });
   const int WS = roundup(h, 64) + 4;                     // = 4 mod 64
   const size_t lds = sizeof(float) * ((size_t)16 * WS + (size_t)kWaves * NBUF * 16 * HS);
   if (lds > (size_t)kLdsBytes) return set_error(TSG_E_LDS, "%s: h=%d needs %zu B of LDS", fn, h, lds);
@@ -1727,23 +1722,24 @@ static int lstm_fwd_impl(const void* Gx, const void* bias, const void* Whh, void
   return check_launch(fn);
 }
 
-static int lstm_bwd_steps(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
-                         void* dG, void* dC_ws, int B, int T, int h, int dtype, int bm, void* stream);
-
-extern "C" int tsg_lstm_bwd(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
-                            void* dG, void* dC_ws, int B, int T, int h, int dtype, void* stream) {
-  return lstm_bwd_steps(WhhT, R, Cs, dOut, dHn, dG, dC_ws, B, T, h, dtype, 0, stream);
+extern "C" int tsg_lstm_fwd(const void* Gx, const void* Whh, void* out, void* R, void* Cs, void* sync_ws, int B, int T, int h, int dtype, void* stream) {
+  return lstm_fwd_impl(Gx, nullptr, Whh, out, R, Cs, sync_ws, sync_ws ? kSyncBytes : 0, B, T, h, dtype, 0, stream);
+}
+extern "C" int tsg_lstm_fwd_bias(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* sync_ws,
+                                 int B, int T, int h, int dtype, int batch_major, void* stream) {
+  return lstm_fwd_impl(Gx, bias, Whh, out, R, Cs, sync_ws, sync_ws ? kSyncBytes : 0, B, T, h, dtype, batch_major, stream);
+}
+extern "C" int tsg_lstm_fwd_ws(const void* Gx, const void* bias, const void* Whh, void* out, void* R, void* Cs, void* ws, long long ws_bytes,
+                               int B, int T, int h, int dtype, int batch_major, void* stream) {
+  if (ws && ws_bytes < kSyncBytes) return set_error(TSG_E_SHAPE, "tsg_lstm_fwd_ws: workspace of %lld bytes is smaller than TSG_LSTM_SYNC_BYTES", ws_bytes);
+  return lstm_fwd_impl(Gx, bias, Whh, out, R, Cs, ws, ws ? ws_bytes : 0, B, T, h, dtype, batch_major, stream);
 }
 
+// ---- backward: the step kernels, the persistent kernel's workspace, LDS and launcher, the plan ----
 static int lstm_bwd_steps(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
                           void* dG, void* dC_ws, int B, int T, int h, int dtype, int bm, void* stream) {
   const char* fn = "tsg_lstm_bwd";
-  for (const void* p : {WhhT, R, Cs, dOut, (const void*)dG, (const void*)dC_ws}) {
-    if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-    if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-  }
-  int rc = lstm_check(fn, B, T, h, dtype);
-  if (rc) return rc;
+  if (int rc = lstm_check_args(fn, {WhhT, R, Cs, dOut, dG, dC_ws}, nullptr, nullptr, B, T, h, dtype)) return rc;
   auto kern = lstm_bwd_step_kernel;
   auto st = static_cast<hipStream_t>(stream);
   const int grid = 2 * cdiv(h, 16) * cdiv(B, 32);
@@ -1752,88 +1748,82 @@ static int lstm_bwd_steps(const void* WhhT, const void* R, const void* Cs, const
                        (const float*)dOut, (const float*)dHn, (float*)dG, (float*)dC_ws, B, T, h, step, bm);
   return check_launch(fn);
 }
-
+extern "C" int tsg_lstm_bwd(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
+                            void* dG, void* dC_ws, int B, int T, int h, int dtype, void* stream) {
+  return lstm_bwd_steps(WhhT, R, Cs, dOut, dHn, dG, dC_ws, B, T, h, dtype, 0, stream);
+}
 extern "C" long long tsg_lstm_bwd_ws_bytes(int B, int T, int h) {
   (void)T;
   if (B <= 0 || h <= 0 || h % 128 || h > kPersistMaxH) return 0;
   const long long nus = h / 32, bslices = cdiv(B, 16);
   return kSyncBytes + 4LL * 2 * bslices * nus * nus * 512 * (long long)sizeof(float);
 }
-
-static constexpr size_t kBwd2Lds = sizeof(float) * ((size_t)kDlFloats + 16 * kPLS + 4 * 16 * kQLS + kObBufs * kObDw + 4);
+// dynamic LDS of lstm_bwd_persist2_kernel: dG tile, partial-dh gather, polled partial sums, streamed operand tiles
+constexpr size_t kBwd2Lds = sizeof(float) * ((size_t)kDlFloats + 16 * kPLS + 4 * 16 * kQLS + kObBufs * kObDw + 4);
 static_assert(kDlFloats >= 16 * kDLS, "dG tile region holds the fp32 tile too");
-static int bwd_persist_capacity() { return persist_capacity(2, lstm_bwd_persist2_kernel<4, 0>, kThreads, kBwd2Lds, 1); }
+// rows c0 .. c0 + Bc - 1 of the layer, seq = their first sequence row; R, dOut and dG in the mode's storage type
+typedef void (*BwdLaunch)(int grid, hipStream_t st, const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn, void* dG,
+                          void* ws, void* dbias, int Bc, int B, int T, int h, int bm, size_t seq, int c0);
+template <int TW, int MODE>
+static void launch_bwd_persist(int grid, hipStream_t st, const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
+                               void* dG, void* ws, void* dbias, int Bc, int B, int T, int h, int bm, size_t seq, int c0) {
+  typedef typename SeqT<MODE>::type GT;
+  const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
+  hipLaunchKernelGGL((lstm_bwd_persist2_kernel<TW, MODE>), dim3(grid), dim3(kThreads), kBwd2Lds, st, (const float*)WhhT,
+                     (const GT*)R + (size_t)c0 * h * 4, (const float*)Cs + (size_t)c0 * h, (const GT*)dOut + seq * H2,
+                     dHn ? (const float*)dHn + (size_t)c0 * h : nullptr, (GT*)dG + seq * K8, (float*)((char*)ws + kSyncBytes), (unsigned*)ws,
+                     (float*)dbias, Bc, B, T, h, launch_flags(), bm, error_sink());
+}
 
-extern "C" int tsg_lstm_bwd_ws_persistent(int B, int T, int h, long long ws_bytes) {
+struct BwdPlan {
+  bool persistent = false;                        // lstm_bwd_persist2_kernel<TW, MODE>; else the step kernels
+  BwdLaunch go = nullptr; const void* kernel = nullptr;   // the launcher and the instantiation it launches (for its LDS attribute)
+  int cap = 0, rows = 0;                          // co-resident workgroups, rows per launch
+};
+template <int TW, int MODE>
+static void bwd_pick(BwdPlan& p) { p.go = launch_bwd_persist<TW, MODE>; p.kernel = reinterpret_cast<const void*>(lstm_bwd_persist2_kernel<TW, MODE>); }
+template <int MODE>
+static void bwd_pick_h(BwdPlan& p, int h) {
+  if (h == 512) bwd_pick<4, MODE>(p); else if (h == 384) bwd_pick<3, MODE>(p); else if (h == 256) bwd_pick<2, MODE>(p); else bwd_pick<1, MODE>(p);
+}
+// THE backward plan.  Persistent when the ring workspace is there (ws_ok: non-NULL and 16-byte aligned; ws_bytes >= tsg_lstm_bwd_ws_bytes,
+// which is 0 unless h is 128 / 256 / 384 / 512), T > 1, the switch allows it -- automatically for T >= 8, except that bf16 storage, which has no
+// step kernels, ignores that rule as in the forward -- and one 16-row slice of h / 32 workgroups can be co-resident.
+static BwdPlan lstm_bwd_plan(int B, int T, int h, int dtype, bool ws_ok, long long ws_bytes) {
+  BwdPlan p;
+  const bool bf = dtype == TSG_BF16;
   const long long need = tsg_lstm_bwd_ws_bytes(B, T, h);
-  return need > 0 && ws_bytes >= need && T > 1 && persist_wanted(T) && persist_chunk_rows(B, h / 32, bwd_persist_capacity()) > 0;
+  if (!(ws_ok && need > 0 && ws_bytes >= need && T > 1 && (bf ? persist_mode() != 0 : persist_wanted(T)))) return p;
+  // (one occupancy answer, that of the largest instantiation, serves all twelve: they share the LDS size and the 512-thread launch bound)
+  p.cap = persist_capacity(lstm_bwd_persist2_kernel<4, 0>, kThreads, kBwd2Lds, 1);
+  p.rows = persist_chunk_rows(B, h / 32, p.cap);
+  p.persistent = p.rows > 0;
+  if (bf) bwd_pick_h<2>(p, h); else if (dtype == TSG_F32S) bwd_pick_h<1>(p, h); else bwd_pick_h<0>(p, h);
+  return p;
 }
 
-extern "C" int tsg_lstm_bwd_ws(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
-                               void* dG, void* dC_ws, void* ws, long long ws_bytes, void* dbias, int B, int T, int h,
-                               int dtype, void* stream) {
-  return tsg_lstm_bwd_ws_layout(WhhT, R, Cs, dOut, dHn, dG, dC_ws, ws, ws_bytes, dbias, B, T, h, dtype, 0, stream);
-}
-
-extern "C" int tsg_lstm_bwd_ws_layout(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn,
-                                      void* dG, void* dC_ws, void* ws, long long ws_bytes, void* dbias, int B, int T, int h,
-                                      int dtype, int batch_major, void* stream) {
+// No dtype argument: the answer is that of the fp32-storage modes (bf16 storage at 2 <= T < 8 runs persistently all the same and fills dbias)
+extern "C" int tsg_lstm_bwd_ws_persistent(int B, int T, int h, long long ws_bytes) { return lstm_bwd_plan(B, T, h, TSG_F32, true, ws_bytes).persistent; }
+extern "C" int tsg_lstm_bwd_ws_layout(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn, void* dG, void* dC_ws,
+                                      void* ws, long long ws_bytes, void* dbias, int B, int T, int h, int dtype, int batch_major, void* stream) {
   const char* fn = "tsg_lstm_bwd_ws";
   const int bm = batch_major != 0;
-  const long long need = tsg_lstm_bwd_ws_bytes(B, T, h);
-  const bool bf = dtype == TSG_BF16;
-  const bool bf_ok = bf && ws && aligned16(ws) && need > 0 && ws_bytes >= need && T > 1 && persist_mode() != 0 &&
-                     persist_chunk_rows(B, h / 32, bwd_persist_capacity()) > 0;
-  if (bf && !bf_ok)
+  const BwdPlan p = lstm_bwd_plan(B, T, h, dtype, ws && aligned16(ws), ws_bytes);
+  // bf16 storage without its kernel: reported before the pointers are looked at
+  if (dtype == TSG_BF16 && !p.persistent)
     return set_error(TSG_E_SHAPE, "%s: dtype TSG_BF16 needs the persistent kernel (ring workspace of tsg_lstm_bwd_ws_bytes, T > 1, h in "
                      "{128,256,384,512}, TSG_LSTM_PERSIST != 0); got T=%d h=%d ws=%lld", fn, T, h, ws_bytes);
-  if (bf_ok || (ws && aligned16(ws) && tsg_lstm_bwd_ws_persistent(B, T, h, ws_bytes))) {
-    for (const void* p : {WhhT, R, Cs, dOut, (const void*)dG}) {
-      if (!p) return set_error(TSG_E_NULL, "%s: NULL pointer argument", fn);
-      if (!aligned16(p)) return set_error(TSG_E_ALIGN, "%s: pointer %p is not 16-byte aligned", fn, p);
-    }
-    int rc = lstm_check(fn, B, T, h, dtype);
-    if (rc) return rc;
-    auto st = static_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;                               // (dbias is zeroed together with the first chunk's sync words: one node)
-    const bool split = dtype == TSG_F32S;
-    const int rows = persist_chunk_rows(B, h / 32, bwd_persist_capacity());      // > 0 (tsg_lstm_bwd_ws_persistent)
-    const size_t K8 = (size_t)8 * h, H2 = (size_t)2 * h;
-    if (bf) {
-      auto pb = h == 512 ? lstm_bwd_persist2_kernel<4, 2> : h == 384 ? lstm_bwd_persist2_kernel<3, 2>
-              : h == 256 ? lstm_bwd_persist2_kernel<2, 2> : lstm_bwd_persist2_kernel<1, 2>;
-      e = allow_lds(pb, kBwd2Lds);
-      if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-      for (int c0 = 0; c0 < B; c0 += rows) {
-        const int Bc = B - c0 < rows ? B - c0 : rows;
-        const size_t seq = bm ? (size_t)c0 * T : (size_t)c0;
-        e = zero3_async(ws, kSyncBytes, c0 == 0 ? dbias : nullptr, sizeof(float) * 8 * h, nullptr, 0, st);
-        if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
-        hipLaunchKernelGGL(pb, dim3(persist_grid(cdiv(Bc, 16), h / 32, bwd_persist_capacity())), dim3(kThreads), kBwd2Lds, st, (const float*)WhhT,
-                           (const lstm_bf16*)R + (size_t)c0 * h * 4, (const float*)Cs + (size_t)c0 * h, (const lstm_bf16*)dOut + seq * H2,
-                           dHn ? (const float*)dHn + (size_t)c0 * h : nullptr, (lstm_bf16*)dG + seq * K8, (float*)((char*)ws + kSyncBytes),
-                           (unsigned*)ws, (float*)dbias, Bc, B, T, h, launch_flags(), bm, error_sink());
-      }
-      return check_launch(fn);
-    }
-    auto pk = h == 512 ? (split ? lstm_bwd_persist2_kernel<4, 1> : lstm_bwd_persist2_kernel<4, 0>)
-            : h == 384 ? (split ? lstm_bwd_persist2_kernel<3, 1> : lstm_bwd_persist2_kernel<3, 0>)
-            : h == 256 ? (split ? lstm_bwd_persist2_kernel<2, 1> : lstm_bwd_persist2_kernel<2, 0>)
-            : (split ? lstm_bwd_persist2_kernel<1, 1> : lstm_bwd_persist2_kernel<1, 0>);
-    e = allow_lds(pk, kBwd2Lds);
-    if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
-    for (int c0 = 0; c0 < B; c0 += rows) {                   // row chunks as in the forward; the ring is reused, dbias accumulates
-      const int Bc = B - c0 < rows ? B - c0 : rows;
-      const size_t seq = bm ? (size_t)c0 * T : (size_t)c0;
-      e = zero3_async(ws, kSyncBytes, c0 == 0 ? dbias : nullptr, sizeof(float) * 8 * h, nullptr, 0, st);
-      if (e != hipSuccess) return set_error((int)e, "%s: memset: %s", fn, hipGetErrorString(e));
-      hipLaunchKernelGGL(pk, dim3(persist_grid(cdiv(Bc, 16), h / 32, bwd_persist_capacity())), dim3(kThreads), kBwd2Lds, st, (const float*)WhhT,
-                         (const float*)R + (size_t)c0 * h * 4, (const float*)Cs + (size_t)c0 * h, (const float*)dOut + seq * H2,
-                         dHn ? (const float*)dHn + (size_t)c0 * h : nullptr, (float*)dG + seq * K8, (float*)((char*)ws + kSyncBytes),
-                         (unsigned*)ws, (float*)dbias, Bc, B, T, h, launch_flags(), bm, error_sink());
-    }
-    return check_launch(fn);
-  }
-  (void)need;
-  return lstm_bwd_steps(WhhT, R, Cs, dOut, dHn, dG, dC_ws, B, T, h, dtype, bm, stream);
+  if (!p.persistent) return lstm_bwd_steps(WhhT, R, Cs, dOut, dHn, dG, dC_ws, B, T, h, dtype, bm, stream);
+  if (int rc = lstm_check_args(fn, {WhhT, R, Cs, dOut, dG}, nullptr, ws, B, T, h, dtype)) return rc;
+  auto st = static_cast<hipStream_t>(stream);
+  const hipError_t e = ensure_lds(p.kernel, kBwd2Lds);
+  if (e != hipSuccess) return set_error((int)e, "%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
+  // row chunks as in the forward; the ring is reused, dbias accumulates: it is zeroed together with the first chunk's sync words (one node)
+  return launch_row_chunks(fn, B, T, bm, p.rows, h / 32, p.cap,
+                           [&](int c0) { return zero3_async(ws, kSyncBytes, c0 == 0 ? dbias : nullptr, sizeof(float) * 8 * h, nullptr, 0, st); },
+                           [&](int grid, int c0, int Bc, size_t seq) { p.go(grid, st, WhhT, R, Cs, dOut, dHn, dG, ws, dbias, Bc, B, T, h, bm, seq, c0); });
+}
+extern "C" int tsg_lstm_bwd_ws(const void* WhhT, const void* R, const void* Cs, const void* dOut, const void* dHn, void* dG, void* dC_ws,
+                               void* ws, long long ws_bytes, void* dbias, int B, int T, int h, int dtype, void* stream) {
+  return tsg_lstm_bwd_ws_layout(WhhT, R, Cs, dOut, dHn, dG, dC_ws, ws, ws_bytes, dbias, B, T, h, dtype, 0, stream);
 }

@@ -2097,6 +2097,40 @@ def _lstm_fwd_ws(B, T, h, device):
     return torch.empty(nb // 4, device=device, dtype=torch.int32), nb
 
 
+def _lstm_recurrence_fwd(Gx, kbias, W_hh, B, T, h, bm, seq_dtype, rec_dtype):
+    """The recurrence of one layer on ``tsg_lstm_fwd_ws``: Gx [rows, 8h] in ``seq_dtype`` (+ ``kbias`` [8h], added inside the kernel, or None)
+    -> (out and R in ``seq_dtype``, Cs fp32, the launch's workspace).  Allocations and call in the order graph capture relies on."""
+    dev = Gx.device
+    out = torch.empty((B, T, 2 * h) if bm else (T, B, 2 * h), device=dev, dtype=seq_dtype)
+    R = torch.empty(T, 2, B, h, 4, device=dev, dtype=seq_dtype)
+    Cs = torch.empty(T, 2, B, h, device=dev, dtype=torch.float32)
+    sync, nws = _lstm_fwd_ws(B, T, h, dev)                             # sync words + the persistent kernel's exchange ring
+    check_lstm_errors()
+    _call("tsg_lstm_fwd_ws", Gx, ptr(Gx), ptr(kbias) if kbias is not None else None, ptr(W_hh), ptr(out), ptr(R), ptr(Cs),
+          ptr(sync), nws, B, T, h, rec_dtype, int(bm))
+    return out, R, Cs, sync
+
+
+def _lstm_recurrence_bwd(W_hh, R, Cs, dOut, B, T, h, bm, seq_dtype, rec_dtype):
+    """The recurrence's backward on ``tsg_lstm_bwd_ws_layout`` -> (dG [.., 2, 4h] in ``seq_dtype``, dbias [8h] fp32 or None).  dbias is the
+    persistent kernel's fused sum of dG: bf16 storage always runs that kernel; the fp32-storage modes ask ``tsg_lstm_bwd_ws_persistent``
+    and return None where the step kernels run (the caller then sums dG)."""
+    dev = dOut.device
+    WhhT = transposed(W_hh)
+    dG = torch.empty((B, T, 2, 4 * h) if bm else (T, B, 2, 4 * h), device=dev, dtype=seq_dtype)
+    dC = torch.empty(2, B, h, device=dev, dtype=torch.float32)
+    nb = int(load().tsg_lstm_bwd_ws_bytes(B, T, h))                      # ring workspace of the persistent backward (0: none)
+    ws = torch.empty(nb // 4 + 4, device=dev, dtype=torch.float32) if nb > 0 else None
+    fused_db = ws is not None and (rec_dtype == TSG_BF16 or bool(load().tsg_lstm_bwd_ws_persistent(B, T, h, nb)))
+    dbias = torch.empty(8 * h, device=dev, dtype=torch.float32) if fused_db else None
+    check_lstm_errors()
+    _gate_before()
+    _call("tsg_lstm_bwd_ws_layout", dOut, ptr(WhhT), ptr(R), ptr(Cs), ptr(dOut), None, ptr(dG), ptr(dC),
+          ptr(ws) if ws is not None else None, nb, ptr(dbias) if fused_db else None, B, T, h, rec_dtype, int(bm))
+    _gate_after()
+    return dG, dbias
+
+
 class _BiLSTMLayer(torch.autograd.Function):
     """One bidirectional LSTM layer from zero state.  x [T,B,I] (time-major) or, with ``bm``, [B,T,I] (batch-major, the
     model's layout: the kernels index the sequence tensors either way, so no transposed copies surround the recurrence);
@@ -2133,16 +2167,9 @@ class _BiLSTMLayer(torch.autograd.Function):
             Gx, kbias = torch.mm(split_bf16x3(x.view(T * B, I), 1, False), ctx.Ws.t(), out_dtype=torch.float32), bias
         else:
             Gx, kbias = _mm(x.view(T * B, I), W_ih.t(), mode), bias           # bias added inside the recurrence kernel
-        out = torch.empty((B, T, 2 * h) if bm else (T, B, 2 * h), device=x.device, dtype=torch.float32)
-        R = torch.empty(T, 2, B, h, 4, device=x.device, dtype=torch.float32)
-        Cs = torch.empty(T, 2, B, h, device=x.device, dtype=torch.float32)
-        sync, nws = _lstm_fwd_ws(B, T, h, x.device)                        # sync words + the persistent kernel's exchange ring
         # outside the strict-fp32 mode the recurrence's W_hh products are split-precision bf16 MFMAs as well (TSG_F32S)
         ctx.rec_dtype = TSG_F32 if mode is None else TSG_F32S
-        check_lstm_errors()
-        _call("tsg_lstm_fwd_ws", x, ptr(Gx), ptr(kbias) if kbias is not None else None, ptr(W_hh), ptr(out), ptr(R), ptr(Cs),
-              ptr(sync), nws, B, T, h, ctx.rec_dtype, int(bm))
-        ctx.lstm_sync = sync
+        out, R, Cs, ctx.lstm_sync = _lstm_recurrence_fwd(Gx, kbias, W_hh, B, T, h, bm, torch.float32, ctx.rec_dtype)
         ctx.bm = bool(bm)
         ctx.save_for_backward(x, W_ih, W_hh, out, R, Cs)
         ctx.mark_non_differentiable(Cs)
@@ -2158,18 +2185,7 @@ class _BiLSTMLayer(torch.autograd.Function):
         h = W_hh.shape[2]
         TB = T * B
         dOut = _f32c(dOut) if dOut is not None else torch.zeros_like(out)
-        WhhT = transposed(W_hh)
-        dG = torch.empty((B, T, 2, 4 * h) if bm else (T, B, 2, 4 * h), device=x.device, dtype=torch.float32)
-        dC = torch.empty(2, B, h, device=x.device, dtype=torch.float32)
-        nb = int(load().tsg_lstm_bwd_ws_bytes(B, T, h))                      # ring workspace of the persistent backward (0: none)
-        ws = torch.empty(nb // 4 + 4, device=x.device, dtype=torch.float32) if nb > 0 else None
-        fused_db = ws is not None and bool(load().tsg_lstm_bwd_ws_persistent(B, T, h, nb))   # persistent path also sums dG -> dbias
-        dbias = torch.empty(8 * h, device=x.device, dtype=torch.float32) if fused_db else None
-        check_lstm_errors()
-        _gate_before()
-        _call("tsg_lstm_bwd_ws_layout", x, ptr(WhhT), ptr(R), ptr(Cs), ptr(dOut), None, ptr(dG), ptr(dC),
-              ptr(ws) if ws is not None else None, nb, ptr(dbias) if fused_db else None, B, T, h, ctx.rec_dtype, int(bm))
-        _gate_after()
+        dG, dbias = _lstm_recurrence_bwd(W_hh, R, Cs, dOut, B, T, h, bm, torch.float32, ctx.rec_dtype)
         dGf = dG.view(TB, 8 * h)
         mode = ctx.mode
         fast = mode == "f32s" and T > 1 and TB % 16 == 0 and h % 4 == 0 and I % 4 == 0
@@ -2260,13 +2276,7 @@ class _BiLSTMLayerBf16(torch.autograd.Function):
             raise ValueError(f"bilstm: shape mismatch x{tuple(x.shape)} W_ih{tuple(W_ih.shape)} W_hh{tuple(W_hh.shape)}")
         Wb = W_ih_bf16 if (W_ih_bf16 is not None and W_ih_bf16.shape == W_ih.shape and W_ih_bf16.dtype == _BF) else weight_bf16(W_ih)     # [8h, I]
         Gx = _mm_bf16_nt(x.view(B * T, I), Wb)                            # bf16 [B*T, 8h]; the bias is added inside the kernel
-        out = torch.empty(B, T, 2 * h, device=x.device, dtype=_BF)
-        R = torch.empty(T, 2, B, h, 4, device=x.device, dtype=_BF)
-        Cs = torch.empty(T, 2, B, h, device=x.device, dtype=torch.float32)
-        sync, nws = _lstm_fwd_ws(B, T, h, x.device)
-        check_lstm_errors()
-        _call("tsg_lstm_fwd_ws", x, ptr(Gx), ptr(bias), ptr(W_hh), ptr(out), ptr(R), ptr(Cs), ptr(sync), nws, B, T, h, TSG_BF16, 1)
-        ctx.lstm_sync = sync
+        out, R, Cs, ctx.lstm_sync = _lstm_recurrence_fwd(Gx, bias, W_hh, B, T, h, True, _BF, TSG_BF16)
         ctx.save_for_backward(x, Wb, W_hh, out, R, Cs)
         ctx.mark_non_differentiable(Cs)
         ctx.set_materialize_grads(False)
@@ -2279,17 +2289,7 @@ class _BiLSTMLayerBf16(torch.autograd.Function):
         h = W_hh.shape[2]
         TB = T * B
         dOut = _bfc(dOut) if dOut is not None else torch.zeros_like(out)
-        WhhT = transposed(W_hh)
-        dG = torch.empty(B, T, 2, 4 * h, device=x.device, dtype=_BF)
-        dC = torch.empty(2, B, h, device=x.device, dtype=torch.float32)
-        nb = int(load().tsg_lstm_bwd_ws_bytes(B, T, h))
-        ws = torch.empty(nb // 4 + 4, device=x.device, dtype=torch.float32)
-        dbias = torch.empty(8 * h, device=x.device, dtype=torch.float32)
-        check_lstm_errors()
-        _gate_before()
-        _call("tsg_lstm_bwd_ws_layout", x, ptr(WhhT), ptr(R), ptr(Cs), ptr(dOut), None, ptr(dG), ptr(dC), ptr(ws), nb, ptr(dbias),
-              B, T, h, TSG_BF16, 1)
-        _gate_after()
+        dG, dbias = _lstm_recurrence_bwd(W_hh, R, Cs, dOut, B, T, h, True, _BF, TSG_BF16)
         dGf = dG.view(TB, 8 * h)
         dx = _mm_bf16_nn(dGf, Wb).view(x.shape) if ctx.needs_input_grad[0] else None
         if _WGRAD_KERNEL and wgrad_f32s_ok(TB, 4 * h, I, h):

@@ -101,6 +101,70 @@ def run_checks(lib):
     eq(lib.tsg_lstm_fwd_bias(p, None, p, p, p, p, p, 4, 16, 100, TSG_BF16, 1, None), -2, "h = 100")
     eq(lib.tsg_lstm_fwd_bias(p, None, p, p, p, p, None, 4, 16, 128, TSG_BF16, 1, None), -2, "no sync workspace")
     eq(lib.tsg_lstm_bwd_ws_layout(p, p, p, p, None, p, p, None, 0, None, 4, 16, 128, TSG_BF16, 1, None), -2, "no ring workspace")
+    # BiLSTM: one argument check for the forward, the step backward and the persistent backward.  Order on the forward (reported under the name
+    # tsg_lstm_fwd): the workspace size (tsg_lstm_fwd_ws only) -> bias alignment -> each pointer's NULL / alignment in argument order ->
+    # workspace alignment -> dtype -> dimensions -> h % 4 -> the bf16 shape.  tsg_lstm_bwd: pointers -> dtype -> dimensions -> h % 4.
+    # tsg_lstm_bwd_ws_layout: the bf16 shape / workspace FIRST (a misaligned workspace counts as none), then -- no GPU here, so the step
+    # kernels' checks under the name tsg_lstm_bwd -- pointers (dC_ws among them) -> dtype -> dimensions -> h % 4.
+    def lf(Gx=p, bias=None, Whh=p, Cs=p, ws=p, nws=2048, B=4, T=16, h=128, dt=TSG_BF16):
+        return lib.tsg_lstm_fwd_ws(Gx, bias, Whh, p, p, Cs, ws, nws, B, T, h, dt, 1, None)
+
+    def lb(WhhT=p, dG=p, B=4, T=16, h=128, dt=TSG_F32):
+        return lib.tsg_lstm_bwd(WhhT, p, p, p, None, dG, p, B, T, h, dt, None)
+
+    def lw(WhhT=p, dOut=p, dC=p, ws=None, nws=0, B=4, T=16, h=128, dt=TSG_F32):
+        return lib.tsg_lstm_bwd_ws_layout(WhhT, p, p, dOut, None, p, dC, ws, nws, None, B, T, h, dt, 1, None)
+    nb = lib.tsg_lstm_bwd_ws_bytes(4, 16, 128)
+    needs_fwd = b"tsg_lstm_fwd: dtype TSG_BF16 needs the persistent kernel (sync_ws given, TSG_LSTM_PERSIST != 0, T > 1, h in {128,256,384,512}); got "
+    needs_bwd = b"tsg_lstm_bwd_ws: dtype TSG_BF16 needs the persistent kernel (ring workspace of tsg_lstm_bwd_ws_bytes, T > 1, h in {128,256,384,512}, " \
+                b"TSG_LSTM_PERSIST != 0); got "
+    k2(lf(Gx=None), -1, b"tsg_lstm_fwd: NULL pointer argument", "lstm fwd: NULL Gx")
+    k2(lf(Whh=p + 4), -3, b"tsg_lstm_fwd: pointer", "lstm fwd: misaligned Whh")
+    k2(lf(bias=p + 4), -3, b"tsg_lstm_fwd: bias", "lstm fwd: misaligned bias")
+    k2(lf(ws=p + 4), -3, b"tsg_lstm_fwd: workspace", "lstm fwd: misaligned workspace")
+    k2(lf(nws=2047), -2, b"tsg_lstm_fwd_ws: workspace of 2047 bytes is smaller than TSG_LSTM_SYNC_BYTES", "lstm fwd: short workspace")
+    k2(lf(nws=2047, dt=TSG_F32), -2, b"smaller than TSG_LSTM_SYNC_BYTES", "lstm fwd: short workspace, fp32")
+    k2(lf(dt=7), -4, b"tsg_lstm_fwd: dtype 7 not supported (TSG_F32, TSG_F32S or TSG_BF16)", "lstm fwd: dtype")
+    for dims in ((0, 16, 128), (4, 0, 128), (4, 16, 0), (-4, 16, 128)):
+        k2(lf(B=dims[0], T=dims[1], h=dims[2], dt=TSG_F32), -2, b"tsg_lstm_fwd: non-positive dimension", f"lstm fwd: dims {dims}")
+    k2(lf(h=6, dt=TSG_F32), -3, b"tsg_lstm_fwd: hidden size 6 must be a multiple of 4", "lstm fwd: h % 4")
+    k2(lf(T=1), -2, needs_fwd + b"T=1 h=128", "lstm fwd: bf16, T = 1")
+    k2(lf(h=96), -2, needs_fwd + b"T=16 h=96", "lstm fwd: bf16, h = 96")
+    k2(lf(ws=None, nws=0), -2, needs_fwd + b"T=16 h=128", "lstm fwd: bf16, no workspace")
+    k2(lf(Gx=None, dt=7), -1, b"NULL pointer argument", "lstm fwd: NULL Gx and dtype 7")
+    k2(lf(bias=p + 4, Gx=None), -3, b"tsg_lstm_fwd: bias", "lstm fwd: misaligned bias and NULL Gx")
+    k2(lf(Gx=p + 4, Cs=None), -3, b"tsg_lstm_fwd: pointer", "lstm fwd: misaligned Gx and NULL Cs: argument order")
+    k2(lf(Gx=None, ws=p + 4), -1, b"NULL pointer argument", "lstm fwd: NULL Gx and misaligned workspace")
+    k2(lf(ws=p + 4, dt=7), -3, b"tsg_lstm_fwd: workspace", "lstm fwd: misaligned workspace and dtype 7")
+    k2(lf(dt=7, B=0), -4, b"dtype 7 not supported", "lstm fwd: dtype 7 and B = 0")
+    k2(lf(B=0, h=6, dt=TSG_F32), -2, b"non-positive dimension", "lstm fwd: B = 0 and h % 4")
+    k2(lf(Gx=None, h=96), -1, b"NULL pointer argument", "lstm fwd: bf16 at h = 96 and NULL Gx")
+    k2(lf(Gx=None, nws=2047), -2, b"smaller than TSG_LSTM_SYNC_BYTES", "lstm fwd: short workspace and NULL Gx")
+    k2(lf(T=1, h=6), -3, b"must be a multiple of 4", "lstm fwd: bf16, T = 1 and h % 4")
+    k2(lb(WhhT=None), -1, b"tsg_lstm_bwd: NULL pointer argument", "lstm bwd: NULL WhhT")
+    k2(lb(dG=p + 4), -3, b"tsg_lstm_bwd: pointer", "lstm bwd: misaligned dG")
+    k2(lb(dt=7), -4, b"tsg_lstm_bwd: dtype 7 not supported", "lstm bwd: dtype")
+    k2(lb(T=0), -2, b"tsg_lstm_bwd: non-positive dimension B=4 T=0 h=128", "lstm bwd: T = 0")
+    k2(lb(h=6), -3, b"tsg_lstm_bwd: hidden size 6 must be a multiple of 4", "lstm bwd: h % 4")
+    k2(lb(WhhT=None, dt=7), -1, b"NULL pointer argument", "lstm bwd: NULL WhhT and dtype 7")
+    k2(lb(dt=7, h=6), -4, b"dtype 7 not supported", "lstm bwd: dtype 7 and h % 4")
+    k2(lw(WhhT=None), -1, b"tsg_lstm_bwd: NULL pointer argument", "lstm bwd_ws: NULL WhhT, no workspace")
+    k2(lw(WhhT=None, ws=p, nws=nb), -1, b"NULL pointer argument", "lstm bwd_ws: NULL WhhT")
+    k2(lw(dOut=p + 4), -3, b"is not 16-byte aligned", "lstm bwd_ws: misaligned dOut")
+    k2(lw(dC=None, ws=p + 4, nws=nb), -1, b"tsg_lstm_bwd: NULL pointer argument", "lstm bwd_ws: misaligned workspace -> the step kernels' check of dC_ws")
+    k2(lw(dC=None, ws=p, nws=2047), -1, b"tsg_lstm_bwd: NULL pointer argument", "lstm bwd_ws: short workspace -> the step kernels' check of dC_ws")
+    k2(lw(dt=7), -4, b"dtype 7 not supported", "lstm bwd_ws: dtype")
+    k2(lw(B=0), -2, b"tsg_lstm_bwd: non-positive dimension", "lstm bwd_ws: B = 0")
+    k2(lw(h=6), -3, b"tsg_lstm_bwd: hidden size 6 must be a multiple of 4", "lstm bwd_ws: h % 4")
+    k2(lw(ws=p, nws=nb, T=1, dt=TSG_BF16), -2, needs_bwd + b"T=1 h=128 ws=%d" % nb, "lstm bwd_ws: bf16, T = 1")
+    k2(lw(ws=p, nws=lib.tsg_lstm_bwd_ws_bytes(4, 16, 96), h=96, dt=TSG_BF16), -2, needs_bwd + b"T=16 h=96 ws=0", "lstm bwd_ws: bf16, h = 96")
+    k2(lw(dt=TSG_BF16), -2, needs_bwd + b"T=16 h=128 ws=0", "lstm bwd_ws: bf16, no workspace")
+    k2(lw(ws=p, nws=nb - 16, dt=TSG_BF16), -2, needs_bwd + b"T=16 h=128 ws=%d" % (nb - 16), "lstm bwd_ws: bf16, short workspace")
+    k2(lw(ws=p + 4, nws=nb, dt=TSG_BF16), -2, needs_bwd, "lstm bwd_ws: bf16, misaligned workspace")
+    k2(lw(WhhT=None, ws=p, nws=nb, T=1, dt=TSG_BF16), -2, needs_bwd, "lstm bwd_ws: bf16 at T = 1 and NULL WhhT: the shape is reported")
+    k2(lw(WhhT=None, B=0, dt=TSG_BF16), -2, needs_bwd, "lstm bwd_ws: bf16, B = 0 and NULL WhhT: the shape is reported")
+    k2(lw(WhhT=None, dt=7), -1, b"NULL pointer argument", "lstm bwd_ws: NULL WhhT and dtype 7")
+    k2(lw(dOut=p + 4, B=0), -3, b"is not 16-byte aligned", "lstm bwd_ws: misaligned dOut and B = 0")
     eq(lib.tsg_match_head_fwd(p, p, p, p, p, 1, 4, 8, 0, 7, None), -4, "dtype")
     eq(lib.tsg_boundary_score_fwd(p, p, p, p, p, None, None, p, p, 1, 4, 4, 7, None), -4, "dtype")
     eq(lib.tsg_error_word(None), 0); eq(lib.tsg_error_sink(None), 0)
